@@ -13,6 +13,15 @@ that) and exits with the first failing rank's status.
 ``--config C3|C4|C5`` runs the SURVEY §8 d companion workloads instead (802.11n, 5G BG2,
 5G BG1); the default C2 line is the one the driver records.
 
+A plain run sets up, warms up, times the K steps and prints the result line: nothing else
+runs on the GPU or the CPU.  ``--dump-outputs DIR`` also writes what the last timed step
+returned to its caller as ``DIR/<name>.npy`` (float64): ``counters.npy``, the int64[4] device
+counters of that one decode (bit errors and frame errors at the last iteration, frames wrong at
+every iteration, loss2), summed over the ranks.  The LLRs come from the seeded Philox stream, so
+the same arguments give the same inputs and, for the integer decoders, the same counters in
+every run and every build.  ``--full`` adds the measurements that take runs of their own:
+``e2e_with_rng``, ``cpu_baseline`` and ``companions`` below.
+
 Prints ONE JSON line (rank 0).  Besides the driver's fields it carries:
   roofline      the dominant kernel against the resource that binds it.  flood (state in HBM):
                 bound "hbm", achieved = SURVEY §8 d bytes/codeword x B / kernel time (HIP
@@ -23,13 +32,14 @@ Prints ONE JSON line (rank 0).  Besides the driver's fields it carries:
                 x_two_kernel_roofline = the §8 d figure / 8 TB/s (a speed-up over the
                 two-kernel design at the HBM roofline) ride along.  traffic = PMC HBM
                 bytes per launch (null without a profile of this kernel at this batch).
-  cpu_baseline  the dense TF-graph-equivalent numpy restatement of the reference decoder
+  cpu_baseline  (--full) the dense TF-graph-equivalent numpy restatement of the reference decoder
                 (oracle/nms_dense.py) on the C1 sample (B=120, T=20, 3.5 dB), rank 0, N=1,
                 sharded over one single-threaded worker process per core of the box's CPU
                 share
-  e2e_with_rng  K steps that each draw a fresh AWGN batch inside the timed region
+  e2e_with_rng  (--full) K steps that each draw a fresh AWGN batch inside the timed region
                 (ldpc_decode_awgn: generated in the decoder's prologue; SURVEY §8 d
                 "separately time end-to-end with GPU RNG and counters")
+  companions    (--full) C3, C4 and C5 timed after the headline of a default one-GPU C2 run
 """
 from __future__ import annotations
 
@@ -182,15 +192,25 @@ def main():
     ap.add_argument("--decoding-type", type=int, default=2, choices=[0, 1, 2, 3],
                     help="0 sum-product, 1 MS fp32, 2 QMS (default), 3 MS without the zero nudge")
     ap.add_argument("--q-bit", type=int, default=5, choices=[6, 5, -5, 4, 3])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the sweep step with "
+                         "the channel generated per step (e2e_with_rng), the CPU baseline and "
+                         "the companion workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (counters.npy, float64[4]) to DIR")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--all-kernels", action="store_true",
                     help="also time the non-default kernel and report it under 'kernels'")
     ap.add_argument("--no-companions", action="store_true",
-                    help="skip the SURVEY 8d companion workloads (C3, C4, C5) a default one-GPU run "
-                         "times after the headline and reports under 'companions'")
+                    help="with --full: skip the SURVEY 8d companion workloads (C3, C4, C5) a "
+                         "default one-GPU run times after the headline and reports under "
+                         "'companions'")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus))
 
@@ -256,6 +276,9 @@ def main():
                          B_max=B)
         llr = dec.awgn(B, sigma, seed=1076, offset=rank * B, punct=punct, short=short)  # in HBM
         counters = torch.zeros(4, dtype=torch.int64, device=dev)
+        # the last timed step accumulates into counters of its own (zeroed here, outside the
+        # timed region): what that one decode returns to its caller, for --dump-outputs
+        last = torch.zeros(4, dtype=torch.int64, device=dev)
         name = dec.kernel_info(T)[1]
         stream = torch.cuda.current_stream(dev)
         for _ in range(args.warmup):      # (the warmups run the timed step: the e2e run's first
@@ -273,24 +296,31 @@ def main():
         t0 = time.perf_counter()
         ev0.record(stream)
         for i in range(args.steps):
+            acc = last if i == args.steps - 1 else counters
             if e2e:                 # a fresh AWGN batch per step, generated by the decoder
                 dec.decode_awgn(B, sigma, seed=1076 + i + 1, offset=rank * B, punct=punct,
-                                short=short, T=T, counters=counters)
+                                short=short, T=T, counters=acc)
             else:
-                dec.decode(llr, T=T, app=False, counters=counters)
+                dec.decode(llr, T=T, app=False, counters=acc)
         ev1.record(stream)
         torch.cuda.synchronize(dev)
         t1 = time.perf_counter()
         barrier()
         elapsed = allreduce(torch.tensor([t1 - t0], dtype=torch.float64, device=dev),
                             dist.ReduceOp.MAX if dist_on else None)
-        cnt = allreduce(counters.clone(), dist.ReduceOp.SUM if dist_on else None)
+        last = allreduce(last, dist.ReduceOp.SUM if dist_on else None)
+        cnt = allreduce(counters.clone(), dist.ReduceOp.SUM if dist_on else None) + last
         kernel_ms = ev0.elapsed_time(ev1) / args.steps
         return dict(name=name, elapsed=float(elapsed.item()), kernel_ms=kernel_ms,
-                    counters=cnt.cpu().tolist(), design_bytes=dec.kernel_info(T)[0])
+                    counters=cnt.cpu().tolist(), last_counters=last.cpu().tolist(),
+                    design_bytes=dec.kernel_info(T)[0])
 
     primary = run(args.kernel)
-    e2e = run(args.kernel, e2e=True)
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "counters.npy"),
+                np.asarray(primary["last_counters"], np.float64))
+    e2e = run(args.kernel, e2e=True) if args.full else None
     extra = {}
     if args.all_kernels:
         for k in ("flood", "fused"):
@@ -391,14 +421,15 @@ def main():
         "counters": {"bit_err_last": c[0], "frame_err_last": c[1], "frame_err_all": c[2],
                      "loss2": c[3], "seed": 1076, "rank_offsets": [r * B for r in range(world)]},
     }
-    out["e2e_with_rng"] = {"codewords_per_s": round(world * B * args.steps / e2e["elapsed"], 1),
-                           "ms_per_step": round(1e3 * e2e["elapsed"] / args.steps, 3)}
+    if e2e:
+        out["e2e_with_rng"] = {"codewords_per_s": round(world * B * args.steps / e2e["elapsed"], 1),
+                               "ms_per_step": round(1e3 * e2e["elapsed"] / args.steps, 3)}
     if extra:
         out["kernels"] = extra
-    if (world == 1 and rank == 0 and not args.no_cpu_baseline and args.config == "C2"
+    if (args.full and world == 1 and rank == 0 and not args.no_cpu_baseline and args.config == "C2"
             and args.decoding_type == 2 and args.q_bit == 5):
         out["cpu_baseline"] = cpu_baseline(proto, g, W, cp, T=T)
-    if (world == 1 and not dist_on and not args.no_companions and args.config == "C2"
+    if (args.full and world == 1 and not dist_on and not args.no_companions and args.config == "C2"
             and args.decoding_type == 2 and args.q_bit == 5 and args.kernel == "auto"
             and args.iters is None and args.snr is None and args.batch == 1 << 20):
         # the other SURVEY 8d workloads (BASELINE configs[2..4]) timed in the same run, so the

@@ -16,7 +16,7 @@ for c in ${CONFIGS:-C2}; do
   cp profiles/traffic_*.json $OUT/ 2>/dev/null
 done
 [ -n "$NO_BENCH" ] && exit 0
-timeout -k 10 600 python3 bench.py > $OUT/bench_c2.json 2> $OUT/bench_c2.err || { tail $OUT/bench_c2.err; exit 1; }
+timeout -k 10 600 python3 bench.py --full > $OUT/bench_c2.json 2> $OUT/bench_c2.err || { tail $OUT/bench_c2.err; exit 1; }
 cat $OUT/bench_c2.json
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/bench_trace -o bench --output-format csv -- python3 bench.py --no-cpu-baseline > $OUT/bench_c2_traced.json 2> $OUT/bench_c2_traced.err || { tail $OUT/bench_c2_traced.err; exit 1; }
 cat $OUT/bench_c2_traced.json

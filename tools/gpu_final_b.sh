@@ -4,8 +4,7 @@ set -o pipefail
 export TMPDIR=/tmp
 TAG=${TAG:-r5z}
 OUT=gpurun_out/ev_$TAG; mkdir -p $OUT
-CONFIGS="C3 C4 C5" bash tools/bench_configs.sh > $OUT/bench_configs.log 2>&1 || { tail -20 $OUT/bench_configs.log; exit 1; }
-cp gpurun_out/bench_C3.json gpurun_out/bench_C4.json gpurun_out/bench_C5.json $OUT/
+CONFIGS="C3 C4 C5" OUT=$OUT bash tools/bench_configs.sh > $OUT/bench_configs.log 2>&1 || { tail -20 $OUT/bench_configs.log; exit 1; }
 cut -c1-300 $OUT/bench_configs.log
 for m in "--decoding-type 1" "--decoding-type 3" "--decoding-type 2 --q-bit 6"; do
   timeout -k 10 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --all-kernels $m > $OUT/b.json 2> $OUT/b.err || { tail $OUT/b.err; exit 1; }

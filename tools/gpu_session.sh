@@ -5,7 +5,7 @@
 # steps:
 #   tests                      pytest -m gpu (-rs: skips named) -> pytest_gpu.log
 #   smoke                      __graft_entry__.smoke()
-#   bench                      default bench.py line (C2, with the CPU baseline) -> bench_c2.json
+#   bench                      bench.py --full line (C2, with the CPU baseline) -> bench_c2.json
 #   configs                    bench.py --config C3 / C4 / C5 -> bench_C*.json
 #   ab:CFG:A.so,B.so:ROUNDS    interleaved A/B of libldpc_nms builds on one config (ms per step)
 #   ablate:CFG:LIB:SET         -DBS_DIAG build, LDPC_DIAG_ABLATE over SET (comma list), timing only
@@ -24,7 +24,7 @@ L=ldpc_error_floor_amd/libldpc_nms.so
 cp $L $OUT/.lib_default.so
 restore() { cp $OUT/.lib_default.so $L; }
 bench_ms() {   # config, extra args -> prints "ms kernel value"
-  timeout -k 10 300 python bench.py --config $1 --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --no-companions $2 > $OUT/.ab.json 2> $OUT/.ab.err || { tail -5 $OUT/.ab.err; return 1; }
+  timeout -k 10 300 python bench.py --full --config $1 --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --no-companions $2 > $OUT/.ab.json 2> $OUT/.ab.err || { tail -5 $OUT/.ab.err; return 1; }
   python -c "import json;d=json.load(open('$OUT/.ab.json'));print(d['ms_per_step'], d['config']['kernel'], d['value'], d['counters']['frame_err_last'], 'e2e', d['e2e_with_rng']['ms_per_step'])"
 }
 for step in "$@"; do
@@ -38,11 +38,11 @@ for step in "$@"; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { cat $OUT/smoke.log; exit 1; }
       cat $OUT/smoke.log ;;
     bench)
-      timeout -k 10 600 python bench.py > $OUT/bench_c2.json 2> $OUT/bench_c2.err || { tail $OUT/bench_c2.err; exit 1; }
+      timeout -k 10 600 python bench.py --full > $OUT/bench_c2.json 2> $OUT/bench_c2.err || { tail $OUT/bench_c2.err; exit 1; }
       cat $OUT/bench_c2.json ;;
     configs)
       for c in ${CONFIGS:-C3 C4 C5}; do
-        timeout -k 10 600 python bench.py --config $c --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_$c.json 2> $OUT/bench_$c.err || { tail $OUT/bench_$c.err; exit 1; }
+        timeout -k 10 600 python bench.py --full --config $c --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_$c.json 2> $OUT/bench_$c.err || { tail $OUT/bench_$c.err; exit 1; }
         python -c "import json;d=json.load(open('$OUT/bench_$c.json'));print('$c', d['value'], d['ms_per_step'], d['config']['kernel'], 'e2e', d['e2e_with_rng']['codewords_per_s'])"
       done ;;
     ab)
