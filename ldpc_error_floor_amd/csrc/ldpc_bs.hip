@@ -79,7 +79,7 @@ __global__ void k_bs_tables(const float* __restrict__ alpha, const float* __rest
 }
 
 // ---- host: planning, graph tables, launch -------------------------------------------------
-typedef int (*LaunchFn)(const BsArgs&, int, int, size_t, hipStream_t, bool);
+typedef int (*LaunchFn)(const BsArgs&, int, int, size_t, hipStream_t, bool, int, int*);
 template <int... I>
 constexpr auto launch_table(std::integer_sequence<int, I...>) {
     return std::array<LaunchFn, sizeof...(I)>{&bs_launch<I>...};
@@ -844,19 +844,29 @@ int bs_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float*
     a.off_preb = p.off_preb;
     a.off_ch = p.off_ch;
     if (const char* e = getenv("LDPC_DIAG_ABLATE")) a.ablate = atoi(e);   // -DBS_DIAG builds
-    const int nblocks = (int)((b.B + PACK - 1) / PACK);
+    const int npacks = (int)((b.B + PACK - 1) / PACK);
+    // the workgroups of the instances with the pack loop (ldpc_bs_kernel.h, BS_LOOP): by default
+    // those resident at once (asked once per context, instance and LDS size: ws.bs_resident);
+    // LDPC_BS_GRID=n launches n (A/B and tests; read at every launch), 0 one per pack
+    int grid = BS_GRID_RESIDENT ? -1 : 0;
+    if (const char* e = getenv("LDPC_BS_GRID")) grid = std::max(atoi(e), 0);
     static const auto kLaunch = launch_table(std::make_integer_sequence<int, kBsNInst>{});
     // (A/B: LDPC_BS_LDS_MIN=bytes requests at least that much dynamic LDS per workgroup, fewer
     // workgroups per CU -- the occupancy experiment; the kernel uses only its own layout)
     static const size_t lds_min = [] { const char* e = getenv("LDPC_BS_LDS_MIN"); return e ? (size_t)atol(e) : 0; }();
     const size_t lds = std::min(std::max(p.lds, lds_min), (size_t)BS_LDS_MAX);
+    const uint64_t rkey = (uint64_t)p.inst << 48 | (uint64_t)p.nw << 32 | (uint64_t)lds;
+    if (ws.bs_resident_key != rkey) {
+        ws.bs_resident_key = rkey;
+        std::fill(ws.bs_resident, ws.bs_resident + 3, 0);
+    }
 #ifdef BS_STAMP
     // diagnostic build: per-wave phase clocks of this decode, printed to stderr
     static unsigned long long* dst = nullptr;
     if (!dst && hipMalloc(reinterpret_cast<void**>(&dst), 256 * 8) != hipSuccess) return LDPC_ERR_OOM;
     if (hipMemsetAsync(dst, 0, 256 * 8, s) != hipSuccess) return LDPC_ERR_HIP;
     a.stamps = dst;
-    st = kLaunch[p.inst](a, nblocks, p.nw, lds, s, b.q8 != nullptr);
+    st = kLaunch[p.inst](a, npacks, p.nw, lds, s, b.q8 != nullptr, grid, ws.bs_resident);
     unsigned long long hst[256];
     if (st != LDPC_OK || hipMemcpyAsync(hst, dst, sizeof(hst), hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
@@ -873,7 +883,7 @@ int bs_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float*
     }
     return st;
 #else
-    return kLaunch[p.inst](a, nblocks, p.nw, lds, s, b.q8 != nullptr);
+    return kLaunch[p.inst](a, npacks, p.nw, lds, s, b.q8 != nullptr, grid, ws.bs_resident);
 #endif
 }
 

@@ -11,8 +11,9 @@ namespace ldpc {
 namespace bs {
 
 template <>
-int bs_launch<BS_INST>(const BsArgs& a, int nblocks, int nw, size_t lds, hipStream_t s, bool q8) {
-    return launch_bs<BS_INST>(a, nblocks, nw, lds, s, q8);
+int bs_launch<BS_INST>(const BsArgs& a, int npacks, int nw, size_t lds, hipStream_t s, bool q8, int grid,
+                       int* resident) {
+    return launch_bs<BS_INST>(a, npacks, nw, lds, s, q8, grid, resident);
 }
 
 }  // namespace bs

@@ -913,6 +913,56 @@ static_assert(!BS_FLOR || BS_TIDFREE, "BS_FLOR: wave 0 folds the words with all 
 #ifndef BS_PROPRIO
 #define BS_PROPRIO -1
 #endif
+// The pack loop: a workgroup of a one-chunk instance decodes packs blockIdx.x, blockIdx.x +
+// gridDim.x, ... instead of one, on a grid of the workgroups that are resident at once
+// (ldpc_bs.hip; LDPC_BS_GRID), so a pack after the first pays no wave launch, no kernel-argument
+// and vn_tab / vn_wdeg loads.  Only what the T loop holds anyway (the lane's slot addresses and
+// variable, the wave's degree bounds) survives the loop back; the check-lane setup, the channel
+// planes and the LDS init are redone per pack.  1: the one-chunk instances without UCN (wman),
+// 2: every one-chunk instance (802.11n too), 0: none (one workgroup per pack)
+#ifndef BS_LOOP
+#define BS_LOOP 1
+#endif
+// the default grid of those instances: 1 the resident workgroups, 0 one workgroup per pack
+#ifndef BS_GRID_RESIDENT
+#define BS_GRID_RESIDENT 1
+#endif
+// (BS_LOOP_VA 1: the slot addresses loaded again per pack instead of carried; A/B switch)
+#ifndef BS_LOOP_VA
+#define BS_LOOP_VA 0
+#endif
+constexpr bool bs_loops(const BsInst& k) {
+    return k.VPL == 1 && k.CPL == 1 && (BS_LOOP == 2 || (BS_LOOP == 1 && !k.UCN));
+}
+// BS_LOOP_TU: this translation unit's instance (ldpc_bs_inst.hip, -DBS_INST=i) has the loop:
+// kBsInst 0-2, and 3 with BS_LOOP 2 (launch_bs_x checks it against bs_loops).  The loop's
+// statements are compiled only there, so the units of the other instances see the kernel text
+// they had before it -- compiled in but constant-false, the added statements alone changed those
+// instances' register allocation (C3 0.5 %, C4 0.4 % slower on one box).
+#if defined(BS_INST) && BS_LOOP
+#define BS_LOOP_TU (BS_INST <= 2 || (BS_LOOP == 2 && BS_INST == 3))
+#else
+#define BS_LOOP_TU 0
+#endif
+// what a pack (index pk) derives from the arguments alone: at the kernel's entry with one pack
+// per workgroup, at each pack's top in the pack loop.  RED: [0] wrong_t, [1] all t, [2] APP > 0,
+// [3] bits; flor: (BS_FLOR) the 32 OR words; ALUT [2][AR][LUT_W], BLUT [2][bcols][BLUT_W];
+// ucn_on(t): UCN work of iteration t's check phase (the syndromes, the alpha' table) and of the
+// hard decisions the variable phase writes for it, skipped where alpha'_t = alpha_t
+#define BS_PACK_SETUP(pk)                                                                          \
+    const int64_t b0 = (int64_t)(pk) * PACK;                                                       \
+    const int nvalid = (int)min<int64_t>(PACK, a.B - b0);                                          \
+    const uint32_t valid = (nvalid >= 32) ? 0xFFFFFFFFu : ((1u << nvalid) - 1u);                   \
+    uint32_t* RED = reinterpret_cast<uint32_t*>(smem + a.off_red);                                 \
+    const int flor = 16 + ((a.T + 3) & ~3);                                                        \
+    const int AR = UCN ? 2 * a.arows : a.arows;                                                    \
+    const int AL = AR * LUT_W, BL = a.bcols * BLUT_W;                                              \
+    uint32_t* ALUT = reinterpret_cast<uint32_t*>(smem + a.off_alut);                               \
+    uint32_t* BLUT = reinterpret_cast<uint32_t*>(smem + a.off_blut);                               \
+    const bool ucn = UCN && a.ucn;                                                                 \
+    auto ucn_on = [&](int t) __attribute__((always_inline)) -> bool {                              \
+        return ucn && (t >= 64 || ((a.ucn_iter >> t) & 1));                                        \
+    };
 
 // Register budget: the small instances run at 64 VGPRs (WPE 8: three 9-wave workgroups per CU).
 // At a 72-register budget only two were resident (the waves of a workgroup are not spread evenly
@@ -965,21 +1015,11 @@ k_bs(BsArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nwv = NT >> 6;
     const int nv = a.n_vars;
-    const int64_t b0 = (int64_t)blockIdx.x * PACK;
-    const int nvalid = (int)min<int64_t>(PACK, a.B - b0);
-    const uint32_t valid = (nvalid >= 32) ? 0xFFFFFFFFu : ((1u << nvalid) - 1u);
-    uint32_t* RED = reinterpret_cast<uint32_t*>(smem + a.off_red);   // [0] wrong_t, [1] all t, [2] APP > 0, [3] bits
-    const int flor = 16 + ((a.T + 3) & ~3);                         // (BS_FLOR) the 32 OR words
-    const int AR = UCN ? 2 * a.arows : a.arows;
-    const int AL = AR * LUT_W, BL = a.bcols * BLUT_W;
-    uint32_t* ALUT = reinterpret_cast<uint32_t*>(smem + a.off_alut);   // [2][AR][LUT_W]
-    uint32_t* BLUT = reinterpret_cast<uint32_t*>(smem + a.off_blut);   // [2][bcols][BLUT_W]
-    const bool ucn = UCN && a.ucn;
-    // UCN work of iteration t's check phase (the syndromes, the alpha' table) and of the hard
-    // decisions the variable phase writes for it: skipped where alpha'_t = alpha_t
-    auto ucn_on = [&](int t) __attribute__((always_inline)) -> bool {
-        return ucn && (t >= 64 || ((a.ucn_iter >> t) & 1));
-    };
+    constexpr bool LOOP = BS_LOOP_TU;              // the pack loop (below)
+    constexpr bool VAPK = LOOP && BS_LOOP_VA;      // the slot addresses loaded per pack
+#if !BS_LOOP_TU
+    BS_PACK_SETUP(blockIdx.x)
+#endif
 
     constexpr int PROPRIO = BS_PROPRIO >= 0 ? BS_PROPRIO
                             : ((BS_PRIO < 0 && VPL == 1 && CPL == 1 && DV >= 6) || BS_PRIO == 4 ? 3 : 0);
@@ -993,7 +1033,7 @@ k_bs(BsArgs a) {
         const uint32_t* vt = a.vn_tab + ((size_t)u * NT + tid) * VNW;
         // (the slot addresses: loaded after the LLR prologue when the lane holds several
         // variables, where they would only add to the registers the LLR loads hold)
-        if (!(BS_LLR_ALL && VPL > 1)) {
+        if (!(BS_LLR_ALL && VPL > 1) && !VAPK) {
 #pragma unroll
             for (int p = 0; p < VNA; ++p) va[u][p] = vt[p];
         }
@@ -1017,6 +1057,46 @@ k_bs(BsArgs a) {
                             (uint32_t)a.stagger_n);
         for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(8);
     }
+    // ---- the packs of this workgroup (BS_LOOP_TU; else the one pack blockIdx.x) ----------------
+    // (the body keeps the indentation it had as the whole kernel)
+#if BS_LOOP_TU
+    auto lane_now = [&]() __attribute__((always_inline)) -> int {
+        uint32_t all = ~0u;
+        asm volatile("" : "+s"(all));
+        return (int)__builtin_amdgcn_mbcnt_hi(all, __builtin_amdgcn_mbcnt_lo(all, 0u));
+    };
+    unsigned pack = blockIdx.x;
+#ifdef BS_STAMP
+    unsigned long long npk = 0ull;
+#endif
+    do {
+    if (pack != blockIdx.x) {
+        // the pack before: its epilogue's reads of RED (and, off the grid, of RED[7]) come before
+        // this pack's init writes
+        __syncthreads();
+        if (PROPRIO > 0) __builtin_amdgcn_s_setprio(PROPRIO);
+    }
+    // What a pack's prologue derives from the kernel arguments and the thread index alone is the
+    // same for every pack, and hoisted over the pack loop it would be held in registers through
+    // the T loop (the first build did: 104 VGPRs and 127 SGPRs spilled on wman).  So each pack
+    // reads the arguments through an opaque copy of the kernel-argument pointer (`a` below: the
+    // pack's view of them, in the constant address space) and computes its thread index again,
+    // from the wave index and mbcnt through an operand that cannot be hoisted (the launch's v0 is
+    // then dead after the entry loads): its prologue is redone, as one pack per workgroup did.
+    typedef __attribute__((address_space(4))) const BsArgs PackArgs;
+    PackArgs* kap = (PackArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kap));
+    PackArgs& a = *kap;
+    const int tid = wave * 64 + lane_now(), lane = tid & 63;
+    BS_PACK_SETUP(pack)
+#define BS_PK pack
+#define BS_NEXT_PACK continue
+#define BS_LANE_IS0 (lane_now() == 0)
+#else
+#define BS_PK blockIdx.x
+#define BS_NEXT_PACK return
+#define BS_LANE_IS0 (lane == 0)
+#endif
     // PAD slot (all ones: V->C negative, magnitude 15), ZERO slot (a zero C->V), the zero hard
     // decision word of UCN padding edges, the counters and the off-grid flag RED[7]; iteration
     // 0's tables are copied global -> LDS asynchronously (global_load_lds) behind the channel
@@ -1039,7 +1119,28 @@ k_bs(BsArgs a) {
     // (the barrier that orders these writes before the channel's flag updates: here when the
     // channel is generated from the sampler's tables; else after the first variable's LLR loads
     // are issued, so that it waits beside their HBM round trip, BS_EB)
-    if constexpr (Q8) gen_tables(a.gen, tid, NT);
+#if BS_LOOP_TU
+    // (the generator's parameters, a copy: the pack's view of the arguments is in the constant
+    // address space)
+    BsGen gen{};
+    if constexpr (Q8) {
+        gen.tab = a.gen.tab;
+        gen.k0 = a.gen.k0;
+        gen.k1 = a.gen.k1;
+        gen.offset = a.gen.offset;
+        gen.nb = a.gen.nb;
+        gen.kmin = a.gen.kmin;
+        gen.ps = a.gen.ps;
+        gen.pe = a.gen.pe;
+        gen.ss = a.gen.ss;
+        gen.se = a.gen.se;
+        gen.lds = a.gen.lds;
+    }
+#define BS_GEN gen
+#else
+#define BS_GEN a.gen
+#endif
+    if constexpr (Q8) gen_tables(BS_GEN, tid, NT);
     if (Q8 || !EBR) __syncthreads();
     BS_ST(8);
     uint32_t cs[VPL], cm[VPL][4], bg[VPL];
@@ -1071,6 +1172,12 @@ k_bs(BsArgs a) {
     // issue variable u + 1's loads while converting variable u's (BS_LLR_ALL), so the fetch is
     // one round trip without holding every variable's 32 values at once
     float xv[VPL][PACK];
+    // (pack loop: defined on every path -- assigned only under [the lane has a variable], the 32
+    // values were carried from one pack to the next, live through the T loop: 100 VGPRs spilled)
+#if BS_LOOP_TU
+#pragma unroll
+    for (int r = 0; r < PACK; ++r) xv[0][r] = 0.f;
+#endif
     if constexpr (Q8) {
         // generated channel (ldpc_decode_awgn): the grid bytes of the lane's variables from the
         // Philox stream, packed into planes as pack_channel's; never off the grid
@@ -1083,7 +1190,7 @@ k_bs(BsArgs a) {
             const int v = var_of(u);
             if (v >= 0 && !ABL(32)) {
                 uint32_t Dq[8];
-                gen_bytes(a.gen, blockIdx.x, v, a.qmax, Dq);
+                gen_bytes(BS_GEN, BS_PK, v, a.qmax, Dq);
                 pack_bytes<BIG>(Dq, valid, cs[u], cm[u], bg[u]);
             }
         }
@@ -1144,10 +1251,10 @@ k_bs(BsArgs a) {
     __syncthreads();
     BS_ST(10);
     if (RED[7]) {                              // off the grid: the v5 fixup decodes this pack
-        if (tid == 0) a.bad[blockIdx.x] = 1u;
-        return;
+        if (tid == 0) a.bad[BS_PK] = 1u;
+        BS_NEXT_PACK;                          // (wave-uniform: every thread read the same word)
     }
-    if (tid == 0) a.bad[blockIdx.x] = 0u;
+    if (tid == 0) a.bad[BS_PK] = 0u;
     if (BS_CH_LDS) {
 #pragma unroll
         for (int u = 0; u < VPL; ++u) {
@@ -1362,7 +1469,7 @@ k_bs(BsArgs a) {
                     if (UCN && !last && v >= 0 && ucn_on(tb)) lds_put(hda, hd);   // HD[v] (Main_Functions.py:184-188)
                     hd &= valid;                                     // APP >= 0 -> hard decision 1
                     if constexpr (XP) {                              // iteration tb - 1's hard decisions
-                        if (v >= 0) a.hdx[((size_t)(tb - 1) * (size_t)((a.B + 31) >> 5) + blockIdx.x) * nv + v] = hd;
+                        if (v >= 0) a.hdx[((size_t)(tb - 1) * (size_t)((a.B + 31) >> 5) + BS_PK) * nv + v] = hd;
                     }
                     if (ABL(8)) hd = 0u;
                     if (counted) {
@@ -1440,7 +1547,7 @@ k_bs(BsArgs a) {
                 apos = wave_or(apos);
                 nb = wave_add(nb);
             }
-            if (lane == 0) {
+            if (BS_LANE_IS0) {
                 if (wr) atomicOr(&RED[0], wr);
                 if (last) {
                     if (apos) atomicOr(&RED[2], apos);
@@ -1450,7 +1557,7 @@ k_bs(BsArgs a) {
         }
     };
 
-    if (BS_LLR_ALL && VPL > 1) {
+    if ((BS_LLR_ALL && VPL > 1) || VAPK) {
 #pragma unroll
         for (int u = 0; u < VPL; ++u) {
             const uint32_t* vt = a.vn_tab + ((size_t)u * NT + tid) * VNW;
@@ -2026,7 +2133,12 @@ k_bs(BsArgs a) {
         e_iter_wrong = ka->iter_wrong;
         e_B = ka->B;
     }
-    if (tid == 0) {
+#if BS_LOOP_TU
+    const int te = wave * 64 + lane_now();   // (`tid` is not held through the T loop)
+#else
+    const int te = tid;
+#endif
+    if (te == 0) {
         const uint32_t wl = RED[0] & valid;
         const uint32_t all = RED[1] & RED[0] & valid;
         const uint32_t ap = RED[2] & valid;
@@ -2045,32 +2157,49 @@ k_bs(BsArgs a) {
     }
     if (e_flags || e_iter_wrong) {
         __syncthreads();
-        if (e_flags && tid < nvalid)
-            e_flags[b0 + tid] = (uint8_t)(((RED[5] >> tid) & 1) | (((RED[6] >> tid) & 1) << 1));
+        if (e_flags && te < nvalid)
+            e_flags[b0 + te] = (uint8_t)(((RED[5] >> te) & 1) | (((RED[6] >> te) & 1) << 1));
         if (e_iter_wrong)                   // [T][packs]: iteration t's frame-error word
-            for (int t = tid; t < a.T; t += NT)
-                e_iter_wrong[(size_t)t * (size_t)((e_B + 31) >> 5) + blockIdx.x] = RED[16 + t] & valid;
+            for (int t = te; t < a.T; t += NT)
+                e_iter_wrong[(size_t)t * (size_t)((e_B + 31) >> 5) + BS_PK] = RED[16 + t] & valid;
     }
-#ifdef BS_STAMP
     BS_ST(5);
+#if BS_LOOP_TU
+#ifdef BS_STAMP
+    ++npk;
+#endif
+    } while ((pack += gridDim.x) < (unsigned)((a.B + PACK - 1) / PACK));
+#elif defined(BS_STAMP)
+    const unsigned long long npk = 1ull;
+#endif
+#undef BS_PK
+#undef BS_NEXT_PACK
+#undef BS_LANE_IS0
+#undef BS_GEN
+#ifdef BS_STAMP
     if (a.stamps && lane == 0 && wave < 16) {
 #pragma unroll
         for (int i = 0; i < 13; ++i) atomicAdd(a.stamps + 16 * wave + i, (unsigned long long)sacc[i]);
-        atomicAdd(a.stamps + 16 * wave + 15, 1ull);
+        atomicAdd(a.stamps + 16 * wave + 15, npk);
         // the SIMD this wave ran on (HW_ID bits 5:4) relative to wave 0's (RED[12]): counts in
         // 32-bit fields, offsets 0-1 in word 13, 2-3 in word 14
         uint32_t hw;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        const uint32_t simd = (((hw >> 4) & 3u) - RED[12]) & 3u;
-        atomicAdd(a.stamps + 16 * wave + 13 + (simd >> 1), 1ull << (32 * (simd & 1)));
+        const uint32_t simd = (((hw >> 4) & 3u) - reinterpret_cast<uint32_t*>(smem + a.off_red)[12]) & 3u;
+        atomicAdd(a.stamps + 16 * wave + 13 + (simd >> 1), npk << (32 * (simd & 1)));
     }
 #endif
 #undef BS_ST
 }
 
+// grid: the workgroups launched; the instances with the pack loop (bs_loops) take any count from 1
+// to the packs, the others exactly one per pack.  *resident (ldpc_bs.hip: one word per context and
+// build): the workgroups of this instance, workgroup size and LDS size that fit the device at
+// once, asked from the runtime when it is 0.
 template <int I, bool XP, bool Q8>
-int launch_bs_x(const BsArgs& a, int nblocks, int nw, size_t lds, hipStream_t s) {
+int launch_bs_x(const BsArgs& a, int npacks, int nw, size_t lds, hipStream_t s, int grid, int* resident) {
     constexpr BsInst k = kBsInst[I];
+    static_assert(bs_loops(k) == (BS_LOOP_TU != 0), "BS_LOOP_TU lists the instances of bs_loops");
     constexpr int LB = (k.VPL > 1 || k.CPL > 1) ? 64 * k.NW : 1024;
     auto* fn = &k_bs<k.D, k.DV, k.LPC, k.VPL, k.CPL, k.UCN, k.BIG, k.PK, k.WPE, XP, LB, Q8>;
     static bool attr = false;
@@ -2079,19 +2208,40 @@ int launch_bs_x(const BsArgs& a, int nblocks, int nw, size_t lds, hipStream_t s)
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)BS_LDS_MAX);
         attr = true;
     }
+    int nblocks = npacks;
+    if constexpr (bs_loops(k)) {
+        if (grid < 0) {                      // (no LDPC_BS_GRID: the resident workgroups)
+            if (*resident <= 0) {
+                int dev = 0, ncu = 0, per_cu = 0;
+                if (hipGetDevice(&dev) != hipSuccess ||
+                    hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+                    hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(fn),
+                                                                 64 * nw, lds) != hipSuccess ||
+                    ncu <= 0 || per_cu <= 0) {
+                    (void)hipGetLastError();
+                    return LDPC_ERR_HIP;
+                }
+                *resident = ncu * per_cu;
+            }
+            grid = *resident;
+        }
+        if (grid > 0 && grid < npacks) nblocks = grid;
+    }
     hipLaunchKernelGGL(fn, dim3(nblocks), dim3(64 * nw), lds, s, a);
     return hipGetLastError() == hipSuccess ? LDPC_OK : LDPC_ERR_HIP;
 }
 template <int I>
-int launch_bs(const BsArgs& a, int nblocks, int nw, size_t lds, hipStream_t s, bool q8) {
+int launch_bs(const BsArgs& a, int npacks, int nw, size_t lds, hipStream_t s, bool q8, int grid, int* resident) {
     // (the generated channel comes from ldpc_decode_awgn, which exports no hard bits)
-    if (a.hdx) return q8 ? LDPC_ERR_UNSUPPORTED : launch_bs_x<I, true, false>(a, nblocks, nw, lds, s);
-    return q8 ? launch_bs_x<I, false, true>(a, nblocks, nw, lds, s) : launch_bs_x<I, false, false>(a, nblocks, nw, lds, s);
+    // (resident[0 / 1 / 2]: the decode, the hard-bit export and the in-prologue channel build)
+    if (a.hdx) return q8 ? LDPC_ERR_UNSUPPORTED : launch_bs_x<I, true, false>(a, npacks, nw, lds, s, grid, resident + 1);
+    return q8 ? launch_bs_x<I, false, true>(a, npacks, nw, lds, s, grid, resident + 2)
+              : launch_bs_x<I, false, false>(a, npacks, nw, lds, s, grid, resident);
 }
 
 // per-instance translation units (ldpc_bs_inst.hip, -DBS_INST=i)
 template <int I>
-int bs_launch(const BsArgs& a, int nblocks, int nw, size_t lds, hipStream_t s, bool q8);
+int bs_launch(const BsArgs& a, int npacks, int nw, size_t lds, hipStream_t s, bool q8, int grid, int* resident);
 
 }  // namespace bs
 }  // namespace ldpc
