@@ -18,7 +18,11 @@ extern "C" {
  * index the kernel reads -- global tables, LDS regions, the dynamic LDS size -- is checked
  * against the allocation.  mode: the internal QMS mode (1 = q 5, 2 = q -5, 3 = q 4, 4 = q 3).
  * flags bit 0 (LDPC_BOUNDS_PRE_GUARD): check the cn_hd read without the `ql < cn_lanes` guard
- * (the round-4 fault), so a test can see the check catch it.  Returns the number of plans
+ * (the round-4 fault), so a test can see the check catch it.  flags bit 1
+ * (LDPC_BOUNDS_BIG_TABLES): take the in-prologue channel's sampler tables to be 4 bytes longer
+ * than the LDS region the plan lends them (the slot region; bsc: the SGN region), wherever the
+ * plan passes the test that lets that build run; the check then reports "channel tables".  Only
+ * the checks read the flags, no kernel or launch path does.  Returns the number of plans
  * checked (>= 0) or a negative status; *violations = out-of-bounds reads found, msg = the
  * first one ("" if none). */
 int ldpc_debug_bs_bounds(const int32_t* proto, int32_t M, int32_t N, int32_t z, int32_t T,

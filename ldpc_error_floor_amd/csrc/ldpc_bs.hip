@@ -98,6 +98,14 @@ struct BsPlan {
     std::vector<int32_t> lay;      // [M][2] first slot of proto row i, stride A_i of its j-blocks
 };
 
+// The in-prologue channel (Q8 builds) copies the sampler's tables, 4 AWGN_TAB_W bytes, into the
+// slot region, which the kernel writes only after the prologue: where the launch puts them
+// (gen.lds) and the test of bs_q8_ok that they fit.  bs_bounds_check holds both against the plan.
+static uint32_t q8_tab_lds(const BsPlan& p) { return p.off_slots; }
+static bool q8_tab_fits(const BsPlan& p) {
+    return (size_t)(p.off_pad - p.off_slots) >= sizeof(uint32_t) * AWGN_TAB_W;
+}
+
 // Column-aligned variable lanes (the one-chunk instances, z <= 32): the variables of each column
 // start a 32-lane half-wave of their own (32 - z idle lanes after them).  Edge f of the z
 // variables of one column reads the slots first + (k mod LPC) A + (k div LPC) z + (hh - shift)
@@ -758,7 +766,7 @@ bool bs_q8_ok(const DevGraph& g, int mode, bool ucn, float clip, int T, bool has
     const BsPlan p = bs_plan(g, mode, ucn, false, clip, T);
     if (!p.ok) return bsc_q8_ok(g, mode, ucn, clip, T, has_short);
     // (the in-prologue channel's tables borrow the slot region)
-    return (!has_short || p.cu > 0.f) && (size_t)(p.off_pad - p.off_slots) >= sizeof(uint32_t) * AWGN_TAB_W;
+    return (!has_short || p.cu > 0.f) && q8_tab_fits(p);
 }
 
 int bs_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode,
@@ -795,7 +803,7 @@ int bs_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float*
         a.gen.pe = g8.pe;
         a.gen.ss = g8.ss;
         a.gen.se = g8.se;
-        a.gen.lds = p.off_slots;
+        a.gen.lds = q8_tab_lds(p);
     }
     a.B = b.B;
     a.n_vars = g.n_vars;
@@ -897,10 +905,11 @@ int bs_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float*
 // (slots, PAD / ZERO, HD, RED, the alpha / beta tables, the per-lane words) and the dynamic LDS
 // size.  The r4c fault (a one-chunk UCN instance read cn_hd for the waves past cn_lanes) is the
 // class it guards: LDPC_BOUNDS_PRE_GUARD drops the `ql < cn_lanes` term of that read, as the
-// kernel had it before the fix, so a test can see the check catch it.
+// kernel had it before the fix, so a test can see the check catch it.  LDPC_BOUNDS_BIG_TABLES
+// (ldpc_fused.h) does the same for the in-prologue channel's sampler tables: the check takes them
+// to be 4 bytes longer than the region the plan lends them.  Only the checks read either flag.
 namespace ldpc {
 namespace bs {
-enum { LDPC_BOUNDS_PRE_GUARD = 1 };
 struct BoundsReport {
     int violations = 0;
     std::string first;
@@ -917,6 +926,10 @@ struct BoundsReport {
     // an LDS byte range [a, a + n) inside [lo, hi)
     void lds(const char* what, long long a, long long n, long long lo, long long hi) {
         if (a < lo || a + n > hi) fail(what, a, hi);
+    }
+    // the LDS byte ranges [a, a + n) and [b, b + m) share no byte
+    void apart(const char* what, long long a, long long n, long long b, long long m) {
+        if (a < b + m && b < a + n) fail(what, a + n, b);
     }
 };
 
@@ -953,11 +966,21 @@ static int bs_bounds_check(const DevGraph& g, const BsPlan& p, const BsHostTable
         for (int w = p.cn_lanes / 64; w < nwv; ++w)
             r.lds("PREB", p.off_preb + 16LL * (64 * w - p.cn_lanes), 16LL * 64, p.off_preb, lds);
     if (UCN) r.lds("HD", 0, 4LL * (nv + 1), 0, p.off_slots);
-    // the in-prologue channel's sampler tables (Q8 builds, gen.lds = off_slots): inside the slot
-    // region, which the kernel writes only after the prologue, and clear of PAD / ZERO / RED /
-    // the tables the prologue writes -- whenever bs_q8_ok lets the Q8 build run on this plan
-    if ((size_t)(p.off_pad - p.off_slots) >= sizeof(uint32_t) * AWGN_TAB_W)
-        r.lds("channel tables", p.off_slots, 4LL * AWGN_TAB_W, p.off_slots, p.off_pad);
+    // the in-prologue channel's sampler tables (Q8 builds), wherever bs_q8_ok's test lets that
+    // build run on this plan: [gen.lds, gen.lds + 4 AWGN_TAB_W) inside the slot region, which the
+    // kernel writes only after the prologue, and clear of the hard decisions, PAD / ZERO, RED and
+    // the alpha / beta tables, which the prologue writes
+    if (q8_tab_fits(p)) {
+        const long long tb = q8_tab_lds(p);
+        const long long tn = (flags & LDPC_BOUNDS_BIG_TABLES) ? (long long)(p.off_pad - p.off_slots) + 4
+                                                              : 4LL * AWGN_TAB_W;
+        r.lds("channel tables", tb, tn, p.off_slots, p.off_pad);
+        if (UCN) r.apart("channel tables / HD", tb, tn, 0, 4LL * (nv + 1));
+        r.apart("channel tables / PAD+ZERO", tb, tn, p.off_pad, 2 * SLOT_B);
+        r.apart("channel tables / RED", tb, tn, p.off_red, (long long)p.off_alut - p.off_red);
+        r.apart("channel tables / ALUT", tb, tn, p.off_alut, 4 * 2 * AL);
+        r.apart("channel tables / BLUT", tb, tn, p.off_blut, 4 * 2 * BL);
+    }
     // ---- variable phase: per (u, lane)
     for (int u = 0; u < VPL; ++u)
         for (int w = 0; w < nwv; ++w) {
@@ -1098,7 +1121,7 @@ extern "C" int ldpc_debug_bs_bounds(const int32_t* proto, int32_t M, int32_t N, 
         if (b1 && !beta_uniform) continue;
         g.w_beta_one = b1;
         BoundsReport r;
-        const int n = bsc_debug_bounds(g, mode, clip, T, r.violations, r.first);
+        const int n = bsc_debug_bounds(g, mode, clip, T, flags, r.violations, r.first);
         if (n <= 0) continue;
         ++checked;
         if (r.violations && first.empty()) first = std::string(b1 ? "bsc beta=1: " : "bsc: ") + r.first;

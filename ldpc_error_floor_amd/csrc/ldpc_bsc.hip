@@ -741,6 +741,12 @@ struct BscPlan {
     std::vector<int32_t> lanes;          // check lane -> check | lane << 16 | lanes per check << 20, -1 idle
 };
 
+// The in-prologue channel (Q8 builds) copies the sampler's tables, 4 AWGN_TAB_W bytes, to LDS
+// byte 0, into the SGN region: where the launch puts them (gen.lds) and the test of bsc_q8_ok
+// that they fit.  bsc_debug_bounds holds both against the plan.
+static uint32_t q8_tab_lds(const BscPlan&) { return 0u; }
+static bool q8_tab_fits(const BscPlan& p) { return (size_t)p.off_a >= sizeof(uint32_t) * AWGN_TAB_W; }
+
 static BscPlan bsc_plan(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T) {
     BscPlan p;
     const char* e = getenv("LDPC_BS");
@@ -997,12 +1003,15 @@ static int bsc_launch(const BscArgs& a, int nblocks, int nw, size_t lds, hipStre
 using namespace bs;
 
 // Host-side bounds check of the bsc plan for this graph (test infrastructure, through
-// ldpc_debug_bs_bounds): the in-prologue channel's tables at LDS byte 0 end inside the SGN
-// region they borrow, and every check chunk's count of real edge positions -- the kernel's
+// ldpc_debug_bs_bounds): wherever bsc_q8_ok's test lets the Q8 build run, the in-prologue
+// channel's tables lie inside the SGN region they borrow and clear of every region after it
+// (LDPC_BOUNDS_BIG_TABLES: taken 4 bytes longer than that region, so a test can see the check
+// fail), and every check chunk's count of real edge positions -- the kernel's
 // wave_or / popc over its lanes, restated -- is in 1 .. EPL, the range the min2 switch covers
 // (its other cases are marked unreachable: BSC_MIN2_U).  Returns 1 if a plan was checked, 0 if
 // none serves the graph; violations / first as BoundsReport.
-int bsc_debug_bounds(const DevGraph& g, int mode, float clip, int T, int& violations, std::string& first) {
+int bsc_debug_bounds(const DevGraph& g, int mode, float clip, int T, int flags, int& violations,
+                     std::string& first) {
     const BscPlan p = bsc_plan(g, mode, false, false, clip, T);
     if (!p.ok) return 0;
     auto fail = [&](const char* what, long long idx, long long lo, long long hi) {
@@ -1015,8 +1024,17 @@ int bsc_debug_bounds(const DevGraph& g, int mode, float clip, int T, int& violat
     const host::GraphTables& h = *g.host;
     const BscInst& k = kBscInst[p.inst];
     const int LPC = k.LPC, EPL = (k.D + LPC - 1) / LPC, z = h.z, nc = g.n_checks;
-    if ((size_t)p.off_a >= sizeof(uint32_t) * AWGN_TAB_W && 4LL * AWGN_TAB_W > (long long)p.off_a)
-        fail("channel tables", 4LL * AWGN_TAB_W, 0, p.off_a);
+    if (q8_tab_fits(p)) {
+        const long long tb = q8_tab_lds(p);
+        const long long tn = (flags & LDPC_BOUNDS_BIG_TABLES) ? (long long)p.off_a + 4 : 4LL * AWGN_TAB_W;
+        if (tb < 0 || tb + tn > (long long)p.off_a) fail("channel tables", tb + tn, 0, p.off_a);
+        // (ARG, REC, TV, RED, ALUT and BLUT, in this order, up to the dynamic LDS size)
+        const long long reg[] = {p.off_a, p.off_rec, p.off_tv, p.off_red, p.off_alut, p.off_blut, (long long)p.lds};
+        static const char* const name[] = {"channel tables / ARG", "channel tables / REC", "channel tables / TV",
+                                           "channel tables / RED", "channel tables / ALUT", "channel tables / BLUT"};
+        for (int i = 0; i < 6; ++i)
+            if (tb < reg[i + 1] && reg[i] < tb + tn) fail(name[i], tb + tn, reg[i], reg[i + 1]);
+    }
     for (int ch = 0; ch < p.cn_lanes / 64; ++ch) {
         const int32_t d0 = p.lanes[(size_t)ch * 64];
         const int Lc = (!k.MIX || d0 < 0 || ((d0 >> 20) & 15) == LPC) ? LPC : LPC / 2;
@@ -1039,7 +1057,7 @@ int bsc_debug_bounds(const DevGraph& g, int mode, float clip, int T, int& violat
 bool bsc_q8_ok(const DevGraph& g, int mode, bool ucn, float clip, int T, bool has_short) {
     const BscPlan p = bsc_plan(g, mode, ucn, false, clip, T);
     // (the in-prologue channel's tables borrow the SGN region at LDS byte 0)
-    return p.ok && (!has_short || p.cu > 0.f) && (size_t)p.off_a >= sizeof(uint32_t) * AWGN_TAB_W;
+    return p.ok && (!has_short || p.cu > 0.f) && q8_tab_fits(p);
 }
 
 bool bsc_supported(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T) {
@@ -1085,7 +1103,7 @@ int bsc_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float
         a.gen.pe = g8.pe;
         a.gen.ss = g8.ss;
         a.gen.se = g8.se;
-        a.gen.lds = 0u;
+        a.gen.lds = q8_tab_lds(p);
     }
 
     a.B = b.B;

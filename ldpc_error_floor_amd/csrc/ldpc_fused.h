@@ -68,8 +68,11 @@ int bs_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float*
 // in the channel, has the shortened-bit marker (a BIG instance)
 bool bs_q8_ok(const DevGraph& g, int mode, bool ucn, float clip, int T, bool has_short);
 bool bsc_q8_ok(const DevGraph& g, int mode, bool ucn, float clip, int T, bool has_short);
-// host-side bounds check of the bsc plan (test infrastructure, ldpc_debug_bs_bounds)
-int bsc_debug_bounds(const DevGraph& g, int mode, float clip, int T, int& violations, std::string& first);
+// host-side bounds check of the bsc plan (test infrastructure, ldpc_debug_bs_bounds), and the
+// flags of that check (include/ldpc_nms_debug.h): no kernel or launch path reads them
+enum { LDPC_BOUNDS_PRE_GUARD = 1, LDPC_BOUNDS_BIG_TABLES = 2 };
+int bsc_debug_bounds(const DevGraph& g, int mode, float clip, int T, int flags, int& violations,
+                     std::string& first);
 // (fused_decode with it: the bit-sliced kernel or LDPC_ERR_UNSUPPORTED)
 bool fused_q8_ok(const DevGraph& g, int mode, int T, float clip, bool ucn, bool per_edge_w, bool has_short);
 // a decode with an in-kernel generator (Bufs::awgn) runs the v5 kernel's prologue channel

@@ -32,6 +32,43 @@ def native_format_uncor_rows(rows):
     return buf.raw[:ln.value]
 
 
+def awgn_tab_w():
+    """``AWGN_TAB_W`` of ``csrc/ldpc_awgn.h``: the words of the sampler tables the in-prologue
+    channel copies into LDS (``bs_q8_ok`` wants 4 of them bytes of slot region), read from the
+    header's own expression."""
+    import re
+    hdr = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                       "ldpc_error_floor_amd", "csrc", "ldpc_awgn.h")
+    expr = re.search(r"constexpr\s+int\s+AWGN_TAB_W\s*=\s*([0-9\s()<+*]+);", open(hdr).read()).group(1)
+    return int(eval(expr, {"__builtins__": {}}))
+
+
+# Synthetic QC proto matrices (int64, -1 = no edge) for the graphs no tuned workload covers.
+def dense16(seed, z):
+    """4 x 16, every entry an edge with a random shift: check degree 16, variable degree 4."""
+    return np.random.RandomState(seed).randint(0, z, size=(4, 16)).astype(np.int64)
+
+
+def vdeg8(seed, z):
+    """8 x 16, irregular: columns 0-1 dense (variable degree 8), columns 2-15 of degree 3 on
+    three distinct random rows; random shifts.  58 proto edges, every check degree >= 2."""
+    rs = np.random.RandomState(seed)
+    P = np.full((8, 16), -1, np.int64)
+    P[:, :2] = rs.randint(0, z, size=(8, 2))
+    for j in range(2, 16):
+        P[rs.choice(8, 3, replace=False), j] = rs.randint(0, z, size=3)
+    return P
+
+
+def row_col_weights(graph, T, seed):
+    """``DecoderWeights`` with a random alpha per (iteration, proto row) in [0.5, 1.0] and a
+    random beta per (iteration, column) in [0.7, 1.2]; no UCN weights."""
+    from ldpc_error_floor_amd.weights import expand_weights
+    rs = np.random.RandomState(seed)
+    return expand_weights((2, 0, 2), {0: rs.uniform(0.5, 1.0, (T, graph.M)),
+                                      2: rs.uniform(0.7, 1.2, (T, graph.N))}, T, graph)
+
+
 def counters_from_app(app):
     """[T, B, Nt] APP -> int64[4] {bit errors @T-1, frames wrong @T-1, frames wrong at every t,
     2*loss} for the all-zero codeword (calc_ber_fer + loss_type 2 semantics)."""
