@@ -28,7 +28,7 @@ namespace bs {
 __global__ void k_bs_tables(const float* __restrict__ alpha, const float* __restrict__ alpha_ucn,
                             const float* __restrict__ beta, const int32_t* __restrict__ row_ptr,
                             int T, int E, int N, int arows, int ar, int bcols, float step, float inv,
-                            int qmax, float cu, uint32_t* alut, uint32_t* blut, int32_t* atid) {
+                            int qmax, float cu, uint32_t* alut, uint32_t* blut) {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;    // one table per thread
     const int na = T * ar, nbt = T * bcols;
     if (f >= na + nbt) return;
@@ -41,22 +41,6 @@ __global__ void k_bs_tables(const float* __restrict__ alpha, const float* __rest
         const float w = al[(size_t)t * E + row_ptr[row]];
         for (int m = 0; m < 16; ++m) g[m] = f5::q_mag5(min(m, qmax), w, step, inv, qmax);
         out = alut + (size_t)f * LUT_W;
-        // the table's index in the fixed set (ldpc_beta_tabs.h), -1 if it is not one of them:
-        // the kernels evaluate a table of the set with immediate truth tables (table_asm2)
-        int id = -1;
-        if (qmax == QMAX) {
-            int sum = 0;
-            for (int m = 0; m < 16; ++m) sum += g[m];
-            for (int k = 0; k < kNBetaTab && id < 0; ++k) {
-                bool eq = true;
-                int sk = 0;
-                for (int m = 0; m < 16; ++m) sk += kBetaTab[k][m];
-                if (sk != sum) continue;
-                for (int m = 0; m < 16; ++m) eq = eq && kBetaTab[k][m] == g[m];
-                if (eq) id = k;
-            }
-        }
-        atid[f] = id;
     } else {
         const int f2 = f - na;
         const int t = f2 / bcols, col = f2 - t * bcols;
@@ -89,7 +73,7 @@ struct BsPlan {
     bool ok = false;
     int inst = -1, nw = 0, cn_lanes = 0, arows = 1, bcols = 1;
     uint32_t off_slots = 0, off_pad = 0, off_zero = 0, off_red = 0, off_alut = 0, off_blut = 0, off_hdz = 0,
-             off_btid = 0, off_ch = 0, off_hdl = 0, off_preb = 0;
+             off_ch = 0, off_hdl = 0;
     int cn_dmin = 0;
     bool ucn = false;
     bool colalign = false;         // variable lanes: each column on a half-wave of its own
@@ -181,7 +165,7 @@ static BsPlan plan_inst(const DevGraph& g, int i, bool ucn, float clip, int min_
     int vch = (nv + 63) / 64;
     const int cch = p.cn_lanes / 64;
     if (k.VPL == 1 && k.CPL == 1) {
-        static const int eca = [] { const char* e = getenv("LDPC_BS_COLALIGN"); return e ? atoi(e) : BS_COLALIGN; }();
+        static const int eca = [] { const char* e = getenv("LDPC_BS_COLALIGN"); return e ? atoi(e) : 1; }();
         p.colalign = eca != 0 && colalign_fits(h, std::max(vch, cch));
         if (p.colalign) vch = (32 * h.N + 63) / 64;
     }
@@ -189,8 +173,8 @@ static BsPlan plan_inst(const DevGraph& g, int i, bool ucn, float clip, int min_
     else p.nw = std::max((vch + k.VPL - 1) / k.VPL, (cch + k.CPL - 1) / k.CPL);
     if (p.nw > 16) return p;                       // 1024-lane workgroup
     if (k.VPL > 1 || k.CPL > 1) {
-        // spread over NW waves (one workgroup per CU); the chunks are dealt to the SIMDs
-        p.nw = k.NW;
+        // spread over 16 waves (one workgroup per CU); the chunks are dealt to the SIMDs
+        p.nw = 16;
         if (vch > k.VPL * p.nw || cch > k.CPL * p.nw) return p;
     }
     // (one alpha / alpha' per iteration: one table pair, read by every lane at the same address,
@@ -222,36 +206,21 @@ static BsPlan plan_inst(const DevGraph& g, int i, bool ucn, float clip, int min_
     p.off_red = (uint32_t)o;
     // + the per-iteration frame-error words, rounded to 16 B: the tables after them are read
     // with ds_read_b128 (T = 50 unrounded put them 8 B off: C3 17.8 -> 24.4 ms, C5 61 -> 81 ms)
-    // and the 32 words the variable phases OR their frame-error words into (BS_FLOR)
-    o += 64 + (((size_t)4 * T + 15) & ~(size_t)15) + 4 * BS_FLORW;
+    // and the FLORW words the variable phases OR their frame-error words into
+    o += 64 + (((size_t)4 * T + 15) & ~(size_t)15) + 4 * FLORW;
     p.off_alut = (uint32_t)o;
     o += (size_t)2 * (k.UCN ? 2 : 1) * p.arows * LUT_W * 4;
     p.off_blut = (uint32_t)o;
     o += (size_t)2 * p.bcols * BLUT_W * 4;
-    if (k.PK && k.CPL == 1 && o > 65535) return p;  // 16-bit alpha-table addresses (BS_PKG)
-    p.off_btid = (uint32_t)o;                      // the next iteration's channel-table ids
-    o += ((size_t)4 * p.bcols + 15) & ~(size_t)15;
-    if (BS_CH_LDS) {                               // the channel planes, 16 B per (lane, variable)
+    if (k.PK && k.CPL == 1 && o > 65535) return p;  // 16-bit alpha-table addresses (PKG)
+    if (k.CPL == 1) {                              // the check lanes' slot-base words
         p.off_ch = (uint32_t)o;
-        o += (size_t)16 * k.VPL * 64 * p.nw;
-    } else if (BS_GBLDS && k.CPL == 1) {           // the check lanes' slot-base words
-        p.off_ch = (uint32_t)o;                    // (BS_ALDS: + their slot addresses, 2 per word)
-        const int EPL = (k.D + k.LPC - 1) / k.LPC;
-        o += (size_t)4 * (BS_ALDS && k.PK ? ((1 + (EPL + 1) / 2) | 1) : 1) * 64 * p.nw;
+        o += (size_t)4 * 64 * p.nw;
     }
-    if (BS_HDLDS && k.UCN && k.CPL == 1) {         // the check lanes' hard-decision addresses
+    if (k.UCN && k.CPL == 1) {                     // the check lanes' hard-decision addresses
         const int EPL = (k.D + k.LPC - 1) / k.LPC, HDW = (EPL + 1) / 2;
         p.off_hdl = (uint32_t)o;
         o += (size_t)4 * HDW * 64 * p.nw;
-    }
-    // the check-idle waves' next channel tables (PREB, ldpc_bs_kernel.h): 16 B per lane of the
-    // waves past cn_lanes
-    const bool preb = (BS_PREB < 0 ? (k.UCN && k.VPL == 1 && k.CPL == 1) : BS_PREB != 0) && k.VPL == 1 &&
-                      k.CPL == 1 && !BS_BTID_LDS;
-    if (preb && p.nw * 64 > p.cn_lanes) {
-        o = (o + 15) & ~(size_t)15;
-        p.off_preb = (uint32_t)o;
-        o += (size_t)16 * (64 * p.nw - p.cn_lanes);
     }
     p.lds = (o + 15) & ~(size_t)15;
     if (p.lds > BS_LDS_MAX) return p;
@@ -276,7 +245,6 @@ BsPlan bs_plan(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float cli
     for (int i = 0; i < kBsNInst; ++i) {
         if (want_lpc != 0 && want_lpc != kBsInst[i].LPC) continue;
         if (want_inst >= 0 && want_inst != i) continue;
-        if (want_inst < 0 && kBsInst[i].NW != 16 && (kBsInst[i].VPL > 1 || kBsInst[i].CPL > 1)) continue;   // A/B only
         BsPlan q = plan_inst(g, i, ucn, clip, min_cdeg, mode, T);
         if (q.ok) return q;
     }
@@ -531,7 +499,7 @@ void bs_stagger(bool one_per_cu, int* stagger, int* stagger_n) {
     *stagger = 0;
     *stagger_n = 0;
     const char* e = getenv("LDPC_BS_STAGGER");
-    const double us = e ? atof(e) : (one_per_cu ? BS_STAGGER_US : 0.0);
+    const double us = e ? atof(e) : (one_per_cu ? STAGGER_US : 0.0);
     if (!(us > 0.0)) return;
     int dev = 0, ncu = 0, khz = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
@@ -546,10 +514,9 @@ void bs_stagger(bool one_per_cu, int* stagger, int* stagger_n) {
 
 // the per-decode weight tables of both bit-sliced kernels (k_bs_tables)
 int bs_make_tables(const Bufs& b, const DevGraph& g, int arows, int ar, int bcols, float step, int qmax,
-                   float cu, bool ucn, FusedWorkspace& ws, uint32_t** alut, uint32_t** blut, hipStream_t s,
-                   const int32_t** atid) {
+                   float cu, bool ucn, FusedWorkspace& ws, uint32_t** alut, uint32_t** blut, hipStream_t s) {
     const size_t na = (size_t)b.T * ar * LUT_W, nb = (size_t)b.T * bcols * BLUT_W;
-    const size_t bytes = (na + nb + (size_t)b.T * ar) * 4;     // + the alpha table ids
+    const size_t bytes = (na + nb) * 4;
     if (bytes > ws.bs_lut_bytes) {
         if (ws.bs_lut) (void)hipFree(ws.bs_lut);
         ws.bs_lut = nullptr;
@@ -560,7 +527,6 @@ int bs_make_tables(const Bufs& b, const DevGraph& g, int arows, int ar, int bcol
     }
     *alut = reinterpret_cast<uint32_t*>(ws.bs_lut);
     *blut = *alut + na;
-    if (atid) *atid = reinterpret_cast<int32_t*>(*blut + nb);
     // (skipped when these tables are already in place: same weights, T and layout)
     const uint64_t kb[4] = {g.w_version, (uint64_t)b.T << 32 | (uint32_t)(arows << 16 | ar),
                             (uint64_t)__builtin_bit_cast(uint32_t, step) << 32 | __builtin_bit_cast(uint32_t, cu),
@@ -572,7 +538,7 @@ int bs_make_tables(const Bufs& b, const DevGraph& g, int arows, int ar, int bcol
     const float* au = (ucn && b.alpha_ucn) ? b.alpha_ucn : b.alpha;
     hipLaunchKernelGGL(k_bs_tables, dim3((unsigned)((ntab + 127) / 128)), dim3(128), 0, s, b.alpha, au,
                        b.beta, g.row_ptr, b.T, g.E, g.N, arows, ar, bcols, step, 1.0f / step, qmax,
-                       cu, *alut, *blut, reinterpret_cast<int32_t*>(*blut + nb));
+                       cu, *alut, *blut);
     return hipGetLastError() == hipSuccess ? LDPC_OK : LDPC_ERR_HIP;
 }
 }  // namespace bs
@@ -783,8 +749,7 @@ int bs_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float*
     const float step = mode_step_bs(mode);
     const int ar = (k.UCN ? 2 : 1) * p.arows;
     uint32_t *alut = nullptr, *blut = nullptr;
-    const int32_t* atid = nullptr;
-    st = bs_make_tables(b, g, p.arows, ar, p.bcols, step, bs_qmax(mode), p.cu, ucn, ws, &alut, &blut, s, &atid);
+    st = bs_make_tables(b, g, p.arows, ar, p.bcols, step, bs_qmax(mode), p.cu, ucn, ws, &alut, &blut, s);
     if (st != LDPC_OK) return st;
     const int DV = k.DV;
     const int VNW = (k.PK ? (DV + 1) / 2 : DV) + 1;
@@ -833,7 +798,6 @@ int bs_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float*
     // the fixed-set channel tables cover the grids whose magnitudes saturate at 15 (q = 5, -5)
     a.btid = (bs_qmax(mode) == QMAX && !getenv("LDPC_BS_NOBFIX")) ? g.beta_tid : nullptr;
     a.btid_n = g.N;
-    a.atid = getenv("LDPC_BS_NOAFIX") ? nullptr : atid;
     a.counters = counters;
     a.flags = flags;
     a.bad = bad;
@@ -847,16 +811,14 @@ int bs_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float*
     a.off_alut = p.off_alut;
     a.off_blut = p.off_blut;
     a.off_hdz = p.off_hdz;
-    a.off_btid = p.off_btid;
     a.off_hdl = p.off_hdl;
-    a.off_preb = p.off_preb;
     a.off_ch = p.off_ch;
     if (const char* e = getenv("LDPC_DIAG_ABLATE")) a.ablate = atoi(e);   // -DBS_DIAG builds
     const int npacks = (int)((b.B + PACK - 1) / PACK);
-    // the workgroups of the instances with the pack loop (ldpc_bs_kernel.h, BS_LOOP): by default
+    // the workgroups of the instances with the pack loop (ldpc_bs_kernel.h, bs_loops): by default
     // those resident at once (asked once per context, instance and LDS size: ws.bs_resident);
     // LDPC_BS_GRID=n launches n (A/B and tests; read at every launch), 0 one per pack
-    int grid = BS_GRID_RESIDENT ? -1 : 0;
+    int grid = -1;
     if (const char* e = getenv("LDPC_BS_GRID")) grid = std::max(atoi(e), 0);
     static const auto kLaunch = launch_table(std::make_integer_sequence<int, kBsNInst>{});
     // (A/B: LDPC_BS_LDS_MIN=bytes requests at least that much dynamic LDS per workgroup, fewer
@@ -946,25 +908,18 @@ static int bs_bounds_check(const DevGraph& g, const BsPlan& p, const BsHostTable
     const long long AL = (long long)AR * LUT_W, BL = (long long)p.bcols * BLUT_W;
     const long long lds = (long long)p.lds;
     const bool SKIPM = CPL > 1;
-    const bool GBL = BS_GBLDS && CPL == 1 && !BS_CH_LDS;
-    const bool HDL = BS_HDLDS && UCN && CPL == 1;
-    // (ALDS: GW words per lane, the slot base and then the packed slot addresses)
-    const int HWA = (EPL + 1) / 2;
-    const int GW = (GBL && k.PK && BS_ALDS) ? ((1 + HWA) | 1) : 1;
+    const bool GBL = CPL == 1;
+    const bool HDL = UCN && CPL == 1;
     // the allocations
     if (getenv("LDPC_BOUNDS_VERBOSE"))
         fprintf(stderr, "bs plan: inst %d nw %d ucn %d lds %lld (slots %u..%u, alut %u, blut %u, ch %u, hdl %u)\n",
                 p.inst, p.nw, (int)p.ucn, lds, p.off_slots, p.off_pad, p.off_alut, p.off_blut, p.off_ch, p.off_hdl);
     r.in("lds size", lds, (long long)BS_LDS_MAX + 1);
     if ((long long)t.vn.size() != (long long)VPL * NT * VNW) r.fail("vn_tab size", (long long)t.vn.size(), (long long)VPL * NT * VNW);
-    r.lds("RED", p.off_red, 4LL * (16 + ((T + 3) & ~3) + BS_FLORW), 0, p.off_alut);
+    r.lds("RED", p.off_red, 4LL * (16 + ((T + 3) & ~3) + FLORW), 0, p.off_alut);
     r.lds("ALUT", p.off_alut, 4 * 2 * AL, 0, p.off_blut);
     r.lds("BLUT", p.off_blut, 4 * 2 * BL, 0, lds);
     r.lds("PAD+ZERO", p.off_pad, 2 * SLOT_B, p.off_slots, p.off_red);
-    // (PREB) the check-idle waves' lanes, 16 B each
-    if (p.off_preb)
-        for (int w = p.cn_lanes / 64; w < nwv; ++w)
-            r.lds("PREB", p.off_preb + 16LL * (64 * w - p.cn_lanes), 16LL * 64, p.off_preb, lds);
     if (UCN) r.lds("HD", 0, 4LL * (nv + 1), 0, p.off_slots);
     // the in-prologue channel's sampler tables (Q8 builds), wherever bs_q8_ok's test lets that
     // build run on this plan: [gen.lds, gen.lds + 4 AWGN_TAB_W) inside the slot region, which the
@@ -1028,7 +983,7 @@ static int bs_bounds_check(const DevGraph& g, const BsPlan& p, const BsHostTable
                     any |= (1u << ((gdeg + LPC - 1) / LPC)) - 1u;
                 }
                 gm = __builtin_popcount(any);
-                // the kernels' switch over the real positions covers 1 .. EPL (BS_MIN2_CASE)
+                // the kernels' switch over the real positions covers 1 .. EPL
                 if (active) r.in("real positions - 1 (the min2 switch)", gm - 1, EPL);
             }
             for (int l = 0; l < 64; ++l) {
@@ -1043,7 +998,7 @@ static int bs_bounds_check(const DevGraph& g, const BsPlan& p, const BsHostTable
                     if (ucn && gchunk >= 0 && guard)
                         for (int pp = 0; pp < HDW; ++pp) r.in("cn_hd", (long long)ql * HDW + pp, (long long)t.chd.size());
                 }
-                if (GBL) r.lds("per-lane words", p.off_ch + 4LL * GW * (64 * w + l), 4LL * GW, p.off_ch, lds);
+                if (GBL) r.lds("per-lane words", p.off_ch + 4LL * (64 * w + l), 4, p.off_ch, lds);
                 if (HDL)
                     for (int pp = 0; pp < HDW; ++pp) r.lds("HD addresses", p.off_hdl + 4LL * (pp * NT + 64 * w + l), 4, p.off_hdl, lds);
                 if (!active) continue;

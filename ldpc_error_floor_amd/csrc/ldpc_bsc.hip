@@ -24,27 +24,8 @@
 
 #include "ldpc_bs_kernel.h"
 
-// the variable places' edge words not made opaque per use (bsl's BS_VAO; A/B switch, off: the C5
-// build then spills 16-17 VGPRs instead of 7)
-#ifndef BSC_TOPO
-#define BSC_TOPO 0     // the loop-top copies' bounds opaque per iteration (A/B switch: C5 46.37
-                       // against 46.34 ms, profiles/r6/session_r6y.log; off)
-#endif
-#ifndef BSC_VAO
-#define BSC_VAO 0
-#endif
-
 namespace ldpc {
 namespace bs {
-
-// the variable phase at the fewest planes of S for each place's largest degree (bsl's BS_SBV;
-// A/B switch)
-#ifndef BSC_SBV
-#define BSC_SBV 1
-#endif
-#ifndef BSC_SBV_SET
-#define BSC_SBV_SET 3   // the lower plane counts that get a copy: 1 seven, 2 eight (A/B)
-#endif
 
 // instances: D = check-degree bound, DVH / DVL = variable-degree bound of a lane's first /
 // other variables, LPC lanes per check, VPL variables and CPL check chunks per lane
@@ -82,8 +63,6 @@ struct BscArgs {
     const uint32_t* alut;        // [T][arows][LUT_W]
     const uint32_t* blut;        // [T][bcols][BLUT_W]
     int arows, bcols;
-    const int32_t* atid;         // one alpha per iteration (arows 1): [T] kBetaTab index of its
-                                 // table (-1: not in the set), or null
     int64_t* counters;
     uint8_t* flags;
     uint32_t* bad;
@@ -97,26 +76,6 @@ struct BscArgs {
 };
 
 typedef unsigned int v2u __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void lds_qput(uint32_t addr, const uint32_t (&x)[4]) {
-    v4u v;
-    v.x = x[0];
-    v.y = x[1];
-    v.z = x[2];
-    v.w = x[3];
-    *reinterpret_cast<LdsQ*>(addr) = v;
-}
-// the fixed-table check weighting for one alpha per iteration (A/B switch, off: C5 62.7 ms with
-// it against 59.6 without, same box (r3i), and 62.8 with it compiled in but turned off at run
-// time (LDPC_BS_NOAFIX=1) — its 18 live operands raise the register pressure of the whole check
-// phase, which costs more than the 30 table operations and 8 LDS reads it saves)
-#ifndef BSC_AFIX
-#define BSC_AFIX 0
-#endif
-// the bit-serial two minima of bsl (min2_bits) in place of the tournament and lane-group merges
-// (A/B switch)
-#ifndef BSC_BSMIN
-#define BSC_BSMIN 1
-#endif
 
 // Check records in blocks of 16: the q1 words of records 16 b .. 16 b + 15 (256 B), then their q2
 // words (256 B), so q2 is q1 + 256 (an instruction offset) and a ds_read_b128 group of 16 lanes
@@ -143,6 +102,9 @@ k_bsc(BscArgs a) {
     constexpr int EPL = (D + LPC - 1) / LPC;
     constexpr int VNW = DVH + 1;
     constexpr int CVW = (EPL + 1) / 2;
+    // plane counts below the place's that get a copy of the variable phase (1 seven, 2 eight):
+    // both, on every instance
+    constexpr int SBSET = 3;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if ((uint32_t)(uintptr_t)smem != 0u) __builtin_trap();          // LDS-absolute addresses
     const int tid = threadIdx.x;
@@ -155,7 +117,7 @@ k_bsc(BscArgs a) {
     const int nvalid = (int)min<int64_t>(PACK, a.B - b0);
     const uint32_t valid = (nvalid >= 32) ? 0xFFFFFFFFu : ((1u << nvalid) - 1u);
     uint32_t* RED = reinterpret_cast<uint32_t*>(smem + a.off_red);
-    const int flor = 16 + ((a.T + 3) & ~3);                         // (BS_FLOR) the 32 OR words
+    const int flor = 16 + ((a.T + 3) & ~3);                         // the FLORW OR words
     const int AL = a.arows * LUT_W, BL = a.bcols * BLUT_W;
     uint32_t* ALUT = reinterpret_cast<uint32_t*>(smem + a.off_alut);
     uint32_t* BLUT = reinterpret_cast<uint32_t*>(smem + a.off_blut);
@@ -212,24 +174,8 @@ k_bsc(BscArgs a) {
             float xv[PACK];
 #pragma unroll
             for (int r = 0; r < PACK; ++r)
-                xv[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(llr_rs, 4 * v, 4 * r * nv, BS_LLR_CPOL));
-            if (BS_PACKT) {
-                off |= pack_channel<true>(xv, a.inv, a.qmax, a.cu, valid, cs[u], cm[u], bg[u]);
-                continue;
-            }
-#pragma unroll
-            for (int r = 0; r < PACK; ++r) {
-                const float x = xv[r] * a.inv;
-                const float xr = rintf(x);
-                const bool big = fabsf(x) == a.cu;
-                off |= ((xr != x || fabsf(xr) > (float)a.qmax) && !big) ? 1 : 0;
-                const int xi = (r < nvalid) ? (big ? (x < 0.f ? -a.qmax : a.qmax) : (int)xr) : 0;
-                const uint32_t m = (uint32_t)(xi < 0 ? -xi : xi);
-                cs[u] |= (xi < 0 ? 1u : 0u) << r;
-                bg[u] |= (big && r < nvalid ? 1u : 0u) << r;
-#pragma unroll
-                for (int p = 0; p < 4; ++p) cm[u][p] |= ((m >> p) & 1u) << r;
-            }
+                xv[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(llr_rs, 4 * v, 4 * r * nv, 0));
+            off |= pack_channel<true>(xv, a.inv, a.qmax, a.cu, valid, cs[u], cm[u], bg[u]);
         }
     }
     if (off) atomicOr(&RED[7], 1u);
@@ -243,7 +189,7 @@ k_bsc(BscArgs a) {
     if (tid < 8)
         reinterpret_cast<uint32_t*>(smem + a.off_rec + rec_off((uint32_t)a.n_checks) + (tid >> 2) * REC_Q2)[tid & 3] = 0u;
     if (tid < 8) RED[tid] = (tid == 1) ? 0xFFFFFFFFu : 0u;
-    if (BS_FLOR && tid < BS_FLORW) RED[flor + tid] = 0u;
+    if (tid < FLORW) RED[flor + tid] = 0u;
     for (int w = tid; w < AL; w += NT) ALUT[w] = a.alut[w];
     for (int w = tid; w < BL; w += NT) BLUT[w] = a.blut[w];
     __syncthreads();
@@ -257,10 +203,11 @@ k_bsc(BscArgs a) {
 #pragma unroll
         for (int u = 0; u < VPL; ++u) {
             const int dvu = u == 0 ? DVH : DVL;
-            if (BS_VSKIP && dw[u] < 0) continue;   // no variable chunk at this (wave, u) place
+            if (dw[u] < 0) continue;   // no variable chunk at this (wave, u) place
+            // (the edge words made opaque per use, as bsl: without it the build spills more)
 #pragma unroll
             for (int p = 0; p < DVH; ++p)
-                if (p < dvu && !BSC_VAO) asm volatile("" : "+v"(va[u][p]));   // (as bsl's BS_VAO)
+                if (p < dvu) asm volatile("" : "+v"(va[u][p]));
             const int v = vv[u] < 0 ? -1 : (vv[u] & 0xFFFF);
             const bool counted = v >= 0 && v < a.target_bits;
             uint32_t lw[1][4];
@@ -286,7 +233,7 @@ k_bsc(BscArgs a) {
             }
             const int dwu = dw[u];
             // the rest at SBX planes of S: the fewest that hold 15 dw + 15 for the place's largest
-            // degree (bsl's BS_SBV; the places past the first hold at most DVL edges)
+            // degree (as bsl; the places past the first hold at most DVL edges)
             auto vbody = [&](auto sbc) __attribute__((always_inline)) {
                 constexpr int SB = decltype(sbc)::value;
                 uint32_t S[SB];
@@ -351,22 +298,18 @@ k_bsc(BscArgs a) {
                 lds_dput(ta + 8, Tv[2], Tv[3]);
                 lds_dput(ta + 16, Tv[4], Tv[5]);
             };
-            if constexpr (BSC_SBV) {
-                auto dispatch = [&](auto smax) __attribute__((always_inline)) {
-                    constexpr int SM = decltype(smax)::value;
-                    if ((BSC_SBV_SET & 1) && dwu * QMAX + QMAX <= 63) vbody(std::integral_constant<int, 7>{});
-                    else if ((BSC_SBV_SET & 2) && SM == 9 && dwu * QMAX + QMAX <= 127)
-                        vbody(std::integral_constant<int, (SM == 9 ? 8 : SM)>{});
-                    else vbody(std::integral_constant<int, SM>{});
-                };
-                constexpr int SBL = (DVL * QMAX + QMAX <= 127) ? 8 : 9;    // places past the first
-                if (u == 0) dispatch(std::integral_constant<int, SB>{});
-                else dispatch(std::integral_constant<int, SBL>{});
-            } else {
-                vbody(std::integral_constant<int, SB>{});
-            }
+            auto dispatch = [&](auto smax) __attribute__((always_inline)) {
+                constexpr int SM = decltype(smax)::value;
+                if ((SBSET & 1) && dwu * QMAX + QMAX <= 63) vbody(std::integral_constant<int, 7>{});
+                else if ((SBSET & 2) && SM == 9 && dwu * QMAX + QMAX <= 127)
+                    vbody(std::integral_constant<int, (SM == 9 ? 8 : SM)>{});
+                else vbody(std::integral_constant<int, SM>{});
+            };
+            constexpr int SBL = (DVL * QMAX + QMAX <= 127) ? 8 : 9;    // places past the first
+            if (u == 0) dispatch(std::integral_constant<int, SB>{});
+            else dispatch(std::integral_constant<int, SBL>{});
         }
-        if (!first && BS_FLOR && !last) {    // (bsl's BS_FLOR: one ds_or per lane into 32 words)
+        if (!first && !last) {               // (as bsl: one ds_or per lane into the FLORW words)
             const uint32_t la = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) & 31u;
             __hip_atomic_fetch_or(RED + flor + la, wr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         } else if (!first) {
@@ -444,47 +387,27 @@ k_bsc(BscArgs a) {
 
     for (int t = 0; t < a.T; ++t) {
         if (wave == 0 && t > 0) {               // (all lanes of wave 0, the same words: bsl)
-            uint32_t w0;
-            if (BS_FLOR) {                        // (the 32 words of iteration t - 1, zeroed again)
-                const uint32_t ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-                const uint32_t x = ln < 32u ? RED[flor + ln] : 0u;
-                if (ln < 32u) RED[flor + ln] = 0u;
-                w0 = wave_or(x);
-            } else {
-                w0 = RED[0];
-                RED[0] = 0u;
-            }
-            RED[16 + t - 1] = w0;                     // (exported after the loop)
+            // (the FLORW words of iteration t - 1, zeroed again)
+            const uint32_t ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+            const uint32_t x = ln < 32u ? RED[flor + ln] : 0u;
+            if (ln < 32u) RED[flor + ln] = 0u;
+            const uint32_t w0 = wave_or(x);
+            RED[16 + t - 1] = w0;                    // (exported after the loop)
             RED[1] &= w0;
         }
         const int nx = (t + 1) & 1;
 #pragma unroll
         for (int u = 0; u < VPL; ++u) asm volatile("" : "+s"(dw[u]));
         // (the lane's variables opaque per iteration: [v >= 0], [v < target bits] compared per
-        // use, not held through the loop as spilled lane masks; BS_VVO as bsl)
-        if (BS_VVO) {
+        // use, not held through the loop as spilled lane masks; as bsl)
 #pragma unroll
-            for (int u = 0; u < VPL; ++u) asm volatile("" : "+v"(vv[u]));
-        }
+        for (int u = 0; u < VPL; ++u) asm volatile("" : "+v"(vv[u]));
         uint32_t rp = rpk;
         asm volatile("" : "+v"(rp));
-        if (t + 1 < a.T) {
-            // (the lane index made opaque per iteration: the copy addresses are recomputed here
-            // rather than hoisted out of the T loop into registers the loop body spills)
-            if (BS_GLDS) {            // (async global -> LDS, retired by the next barrier: bsl)
-                // (BSC_TOPO: the bounds opaque per iteration, as bsl's BS_TOPO)
-                int cw = wave, al = AL, bl = BL, bcl = a.bcols;
-                if (BSC_TOPO) asm volatile("" : "+s"(cw), "+s"(al), "+s"(bl), "+s"(bcl));
-                copy_async(a.off_alut + 4u * (uint32_t)(nx * al), a.alut + (size_t)(t + 1) * al, al, cw, NT);
-                if (bcl > 1)
-                    copy_async(a.off_blut + 4u * (uint32_t)(nx * bl), a.blut + (size_t)(t + 1) * bl, bl, cw, NT);
-            } else {
-                int tl = tid;
-                asm volatile("" : "+v"(tl));
-                for (int w = tl; w < AL; w += NT) ALUT[nx * AL + w] = a.alut[(size_t)(t + 1) * AL + w];
-                if (a.bcols > 1)
-                    for (int w = tl; w < BL; w += NT) BLUT[nx * BL + w] = a.blut[(size_t)(t + 1) * BL + w];
-            }
+        if (t + 1 < a.T) {            // (async global -> LDS, retired by the next barrier: bsl)
+            copy_async(a.off_alut + 4u * (uint32_t)(nx * AL), a.alut + (size_t)(t + 1) * AL, AL, wave, NT);
+            if (a.bcols > 1)
+                copy_async(a.off_blut + 4u * (uint32_t)(nx * BL), a.blut + (size_t)(t + 1) * BL, BL, wave, NT);
         }
         // ======== check nodes ===================================================================
 #pragma unroll
@@ -545,85 +468,36 @@ k_bsc(BscArgs a) {
                     ns[m] = ~0u;
                 }
             }
-            // two minima by a tournament (sorted pairs merged, as bsl); positions past the chunk's
-            // bound hold the all-ones padding, so a pair that straddles it sorts correctly and its
-            // padding sign word, XORed by all L lanes of the group, leaves the parity unchanged
+            // two minima by the bit-serial search of bsl (min2_bits) over the chunk's real positions
+            // (1 <= gmc <= EPL for an active chunk: the other counts are marked unreachable);
+            // positions past the chunk's bound hold the all-ones padding, whose sign word, XORed
+            // by all L lanes of the group, leaves the parity unchanged
             uint32_t m1[4], m2[4];
-            uint32_t cand[BSC_BSMIN ? EPL : 1];
+            uint32_t cand[EPL];
             uint32_t par = ns[0] ^ ns[1];
-            if constexpr (BSC_BSMIN) {
-                // the bit-serial search of bsl (min2_bits), over the chunk's real positions
 #pragma unroll
-                for (int m = 2; m < EPL; ++m) par ^= ns[m];
-                switch (gmc) {
+            for (int m = 2; m < EPL; ++m) par ^= ns[m];
+            switch (gmc) {
 #define BSC_MIN2_CASE(k)                                                                           \
     case k:                                                                                        \
         if constexpr (k <= EPL) {                                                                  \
             min2_bits<k, L>(m1, m2, cand, Xs);                                                     \
-            if (BS_MIN2_Z) {                                                                       \
-                _Pragma("unroll") for (int m = k; m < EPL; ++m) cand[m] = 0u;                      \
-            }                                                                                      \
-        } else if (BSC_MIN2_U) {                                                                   \
+            _Pragma("unroll") for (int m = k; m < EPL; ++m) cand[m] = 0u;                          \
+        } else {                                                                                   \
             __builtin_unreachable();                                                               \
         }                                                                                          \
         break;
-                    BSC_MIN2_CASE(1) BSC_MIN2_CASE(2) BSC_MIN2_CASE(3) BSC_MIN2_CASE(4) BSC_MIN2_CASE(5)
-                    BSC_MIN2_CASE(6) BSC_MIN2_CASE(7) BSC_MIN2_CASE(8) BSC_MIN2_CASE(9) BSC_MIN2_CASE(10)
+                BSC_MIN2_CASE(1) BSC_MIN2_CASE(2) BSC_MIN2_CASE(3) BSC_MIN2_CASE(4) BSC_MIN2_CASE(5)
+                BSC_MIN2_CASE(6) BSC_MIN2_CASE(7) BSC_MIN2_CASE(8) BSC_MIN2_CASE(9) BSC_MIN2_CASE(10)
 #undef BSC_MIN2_CASE
-                    default:
-                        if (BSC_MIN2_U) __builtin_unreachable();  // (an active chunk: 1 <= gmc <= EPL)
-                        break;
-                }
-                par ^= qperm<QP_X1>(par);
-                if (L == 4) par ^= qperm<QP_X2>(par);
-            } else {
-            sort2(m1, m2, Xs[0], Xs[1]);
-#pragma unroll
-            for (int m = 2; m + 1 < EPL; m += 2) {
-                if (m >= gmc) continue;
-                uint32_t b1[4], b2[4];
-                sort2(b1, b2, Xs[m], Xs[m + 1]);
-                merge2(m1, m2, b1, b2);
-                par ^= ns[m] ^ ns[m + 1];
-            }
-            if constexpr (EPL & 1) {
-                if (EPL - 1 < gmc) {
-                    const uint32_t(&X)[4] = Xs[EPL - 1];
-                    const uint32_t l1 = lt4(X, m1), l2 = lt4(X, m2);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        m2[i] = mux(l1, m1[i], mux(l2, X[i], m2[i]));
-                        m1[i] = mux(l1, X[i], m1[i]);
-                    }
-                    par ^= ns[EPL - 1];
-                }
+                default:
+                    __builtin_unreachable();
             }
             par ^= qperm<QP_X1>(par);
-            merge_lanes<QP_X1>(m1, m2);
-            if (L == 4) {
-                par ^= qperm<QP_X2>(par);
-                merge_lanes<QP_X2>(m1, m2);
-            }
-            }
-            // weighted, quantized minima (Main_Functions.py:266-316).  One table of the fixed set
-            // for the whole iteration (uniform alpha: C5): all 4 bits of both by immediate truth
-            // tables (one entry of the jump table for all waves: no instruction-cache churn), the
-            // group's first lane writes the record
-            bool fixed = false;
-            if (BSC_AFIX && a.atid) {
-                const int k = __builtin_amdgcn_readfirstlane(a.atid[t]);
-                if (k >= 0 && k < kNBetaTab) {
-                    fixed = true;
-                    uint32_t p1[4], p2[4];
-                    table_asm2(p1, p2, m1, m2, k);
-                    if (has_check && cjl == 0) {
-                        lds_qput(grec[c], p1);
-                        lds_qput(grec[c] + REC_Q2, p2);
-                    }
-                }
-            }
+            if (L == 4) par ^= qperm<QP_X2>(par);
+            // weighted, quantized minima (Main_Functions.py:266-316)
             uint32_t qb[OBL][2];
-            if (!fixed) {
+            {
                 const uint32_t mm[2][4] = {{m1[0], m1[1], m1[2], m1[3]}, {m2[0], m2[1], m2[2], m2[3]}};
                 const uint32_t tab = gtab[c] + (uint32_t)((t & 1) * AL * 4);
 #pragma unroll
@@ -637,7 +511,7 @@ k_bsc(BscArgs a) {
             // the record: lane j writes planes OBL j .. of q1 and q2 (the whole group has read the
             // old record above: same wave, LDS operations in program order); idle lanes past
             // the last check (degree 0) share its clamped record address and must not write
-            if (!fixed && has_check) {
+            if (has_check) {
 #pragma unroll
                 for (int b = 0; b < OBL; ++b) {
                     lds_put(grec[c] + 4u * (uint32_t)(OBL * cjl + b), qb[b][0]);
@@ -649,18 +523,8 @@ k_bsc(BscArgs a) {
             for (int m = 0; m < EPL; ++m) {
                 if (real(m)) {
                     const uint32_t sa = sbase + m * sstride;
-                    uint32_t eq;
-                    if constexpr (BSC_BSMIN) {
-                        eq = cand[m];
-                    } else {
-                    const uint32_t(&X)[4] = Xs[m];
-                    uint32_t ne = X[0] ^ m1[0];
-#pragma unroll
-                    for (int i = 1; i < 4; ++i) ne = B3(T_ORXOR, ne, X[i], m1[i]);
-                    eq = ~ne;
-                    }
                     lds_put(sa, par ^ ns[m]);
-                    lds_put(sa + a.off_a, eq);
+                    lds_put(sa + a.off_a, cand[m]);
                 }
             }
                     };
@@ -718,8 +582,7 @@ std::vector<int> check_chunk_cost(const host::GraphTables& h, int LPC, int cch);
 std::vector<int> column_rotation(const host::GraphTables& h, int LPC, int EPL, int cn_lanes);
 void bs_stagger(bool one_per_cu, int* stagger, int* stagger_n);
 int bs_make_tables(const Bufs& b, const DevGraph& g, int arows, int ar, int bcols, float step, int qmax,
-                   float cu, bool ucn, FusedWorkspace& ws, uint32_t** alut, uint32_t** blut, hipStream_t s,
-                   const int32_t** atid = nullptr);
+                   float cu, bool ucn, FusedWorkspace& ws, uint32_t** alut, uint32_t** blut, hipStream_t s);
 bool bs_mode(int mode);
 float bs_step(int mode);
 int bs_qmax(int mode);
@@ -847,7 +710,7 @@ static BscPlan bsc_plan(const DevGraph& g, int mode, bool ucn, bool per_edge_w, 
         o += (size_t)nv * 24;
         o = (o + 15) & ~(size_t)15;
         q.off_red = (uint32_t)o;
-        o += 64 + (((size_t)4 * T + 15) & ~(size_t)15) + 4 * BS_FLORW;   // + the frame-error words
+        o += 64 + (((size_t)4 * T + 15) & ~(size_t)15) + 4 * FLORW;      // + the frame-error words
                                                                        // (16 B aligned), the OR words
         q.off_alut = (uint32_t)o;
         o += (size_t)2 * q.arows * LUT_W * 4;
@@ -1008,7 +871,7 @@ using namespace bs;
 // (LDPC_BOUNDS_BIG_TABLES: taken 4 bytes longer than that region, so a test can see the check
 // fail), and every check chunk's count of real edge positions -- the kernel's
 // wave_or / popc over its lanes, restated -- is in 1 .. EPL, the range the min2 switch covers
-// (its other cases are marked unreachable: BSC_MIN2_U).  Returns 1 if a plan was checked, 0 if
+// (its other cases are marked unreachable).  Returns 1 if a plan was checked, 0 if
 // none serves the graph; violations / first as BoundsReport.
 int bsc_debug_bounds(const DevGraph& g, int mode, float clip, int T, int flags, int& violations,
                      std::string& first) {
@@ -1083,8 +946,7 @@ int bsc_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float
     const BscInst& k = kBscInst[p.inst];
     const float step = bs_step(mode);
     uint32_t *alut = nullptr, *blut = nullptr;
-    const int32_t* atid = nullptr;
-    st = bs_make_tables(b, g, p.arows, p.arows, p.bcols, step, bs_qmax(mode), p.cu, false, ws, &alut, &blut, s, &atid);
+    st = bs_make_tables(b, g, p.arows, p.arows, p.bcols, step, bs_qmax(mode), p.cu, false, ws, &alut, &blut, s);
     if (st != LDPC_OK) return st;
     const uint32_t* gt = reinterpret_cast<const uint32_t*>(ws.bs_graph);
     const int VNW = k.DVH + 1;
@@ -1127,7 +989,6 @@ int bsc_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float
     a.cn_lane = reinterpret_cast<const int32_t*>(a.cn_var + (size_t)p.cn_lanes * ((((k.D + k.LPC - 1) / k.LPC) + 1) / 2));
     bs_stagger(false, &a.stagger, &a.stagger_n);     // (LDPC_BS_STAGGER still applies; C5: no gain)
     a.alut = alut;
-    a.atid = (p.arows == 1 && !getenv("LDPC_BS_NOAFIX")) ? atid : nullptr;
     a.blut = blut;
     a.arows = p.arows;
     a.bcols = p.bcols;

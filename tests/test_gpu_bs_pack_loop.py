@@ -1,4 +1,4 @@
-"""The pack loop of the one-chunk bit-sliced kernel (csrc/ldpc_bs_kernel.h, BS_LOOP; GPU only): a
+"""The pack loop of the one-chunk bit-sliced kernel (csrc/ldpc_bs_kernel.h, bs_loops; GPU only): a
 workgroup decodes packs blockIdx.x, blockIdx.x + gridDim.x, ... on a grid of LDPC_BS_GRID
 workgroups (default: those resident at once; 0: one workgroup per pack).  Whatever the grid, the
 APP, hard decisions, frame flags, counters and per-iteration frame-error words must equal those

@@ -1,7 +1,7 @@
 """The bit-sliced kernels' variable phase runs at the fewest planes of S each place's largest
-degree allows (ldpc_bs_kernel.h BS_SBV, ldpc_bsc.hip BSC_SBV: 7 planes where 15 dw + 15 <= 63, 8
+degree allows (ldpc_bs_kernel.h and ldpc_bsc.hip, SBSET: 7 planes where 15 dw + 15 <= 63, 8
 where <= 127, else 9), and 802.11n keeps every C->V of its degree-4 variables in registers
-(BS_KEEP_DV).  These bounds are tight exactly when every message is saturated, so the decodes
+(KEEP).  These bounds are tight exactly when every message is saturated, so the decodes
 here drive them there: channel LLRs at the largest grid magnitude (a very high SNR) with a share
 of their signs flipped, and the trained / flat weights scaled up so that Q(beta ch) and
 Q(alpha m) saturate too.  Counters, frame flags and per-iteration frame-error words must equal

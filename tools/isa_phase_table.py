@@ -29,9 +29,9 @@ the split is the marked build's, the totals of both are printed.  The last itera
 the variable phase (markers K >= 100) is reported separately; the table is one non-last
 iteration, i.e. per pack-edge-iteration for T >> 1.
 
-  --sbv MAX,SET   the plane-count copies of the variable phase (BS_SBV: markers carry
+  --sbv MAX,SET   the plane-count copies of the variable phase (markers carry
                   1000 (planes - 6)) weighted by the places that run each: MAX the instance's
-                  planes of S, SET its BS_SBV_SET (1 seven, 2 eight)
+                  planes of S, SET its SBSET in k_bs / k_bsc (1 seven, 2 eight)
   --mc NW,VPL,CPL --vchunks D,... --cchunks G,...
                   multi-chunk instances: the host's dealing of the variable chunks (largest
                   degree each) and check chunks (real positions each) to (wave, place) slots is
@@ -265,7 +265,7 @@ def main():
                     "weights come from the host's dealing of the chunks to (wave, place) slots")
     ap.add_argument("--vchunks", help="--mc: each variable chunk's largest degree, in chunk order")
     ap.add_argument("--cchunks", help="--mc: each check chunk's real edge positions per lane (gm)")
-    ap.add_argument("--sbv", help="MAX,SET: the instance's planes of S and its BS_SBV_SET (the "
+    ap.add_argument("--sbv", help="MAX,SET: the instance's planes of S and its SBSET (the "
                     "plane-count copies' markers carry 1000 (planes - 6))")
     ap.add_argument("--dump", help="print the static VALU mnemonics of these phases (comma list)")
     ap.add_argument("--json")
@@ -284,7 +284,7 @@ def main():
         cplaces = [[cg[cs[w * cpl + c]] for w in range(nw) if cs[w * cpl + c] >= 0] for c in range(cpl)]
         mc = (nw, places, cplaces)
 
-    def planes(d):        # the variable-phase copy a place of largest degree d runs (BS_SBV)
+    def planes(d):        # the variable-phase copy a place of largest degree d runs (SBSET)
         if not a.sbv:
             return None
         smax, sset = (int(x) for x in a.sbv.split(","))

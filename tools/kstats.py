@@ -2,7 +2,7 @@
 """Register use, spills and static instruction counts of every kernel in one translation unit
 (device-only assembly), for before/after checks of a kernel edit without a GPU:
 
-    python3 tools/kstats.py ldpc_bs_inst.hip -DBS_INST=0 [-DBS_KEEP=4 ...]
+    python3 tools/kstats.py ldpc_bs_inst.hip -DBS_INST=0 [-DBS_MARK ...]
     python3 tools/kstats.py ldpc_bsc.hip
 
 Prints per kernel: VGPRs, SGPRs, VGPR/SGPR spills, LDS (static), and the number of VALU / LDS /
