@@ -169,6 +169,53 @@ int ldpc_decode_awgn(ldpc_ctx* ctx, int64_t B, const ldpc_decode_params* params,
 int ldpc_awgn_in_kernel(const ldpc_ctx* ctx, const ldpc_decode_params* params, int32_t has_short,
                         int32_t app);
 
+/* Syndrome-based early termination (opt-in).  These entry points have NO
+   counterpart in the reference, whose unrolled graph always runs T iterations: their results are
+   defined here and are not compute_results' numbers.  Per codeword b, for the all-zero codeword,
+   with hd_t = (APP_t >= 0) and s_t the syndrome of hd_t over all M*z checks and N*z variables:
+     stop(b)   = the smallest t in [0, T) with s_t == 0, else T - 1;
+     n_iter(b) = stop(b) + 1, in [1, T] (at least one iteration always runs);
+   the frame's outputs are frozen at stop(b), whatever s_t does later, and do not depend on which
+   other codewords share its pack or batch.
+     counters[0] += the ones among the first target_bits of hd_stop
+     counters[1] += [hd_stop has a one among them]
+     counters[2] += [the frame was wrong at every t <= stop(b)]
+     counters[3]    is left untouched (the loss is a training quantity)
+     frame_flags[b] bit 0 = wrong at every t <= stop, bit 1 = wrong at stop (as
+                    ldpc_collect_frames reads them)
+     n_iter[b]      uint8 [B], or NULL
+     iter_hist[t]  += the frames with n_iter == t + 1; int64 [T], or NULL
+   Input LLRs must lie on the quantizer grid (shortened bits at +-clip_llr allowed); the
+   library's own channel produces such LLRs.  A pack of 32 codewords (b / 32) holding an off-grid
+   value is not decoded: its frames get n_iter = 0 and frame_flags = 0x80 and enter neither the
+   counters nor the histogram.
+   Served: QMS with q_bit 5, -5, 4 or 3, no per-edge check weights, kernel AUTO or FUSED,
+   T <= T_max, a graph one of the bit-sliced kernel's early-stop instances fits (one 32-codeword
+   pack per workgroup: wman- and 802.11n-sized graphs).  Anything else returns
+   LDPC_ERR_UNSUPPORTED with nothing launched and no partial result.  ldpc_ctx_last_kernel
+   reports "bsl[...,es]" (and "+gen" when the channel was generated in the kernel).
+   size: sizeof(ldpc_es_outputs) of the caller's header; any other value -> LDPC_ERR_ARG. */
+typedef struct ldpc_es_outputs {
+    int32_t size;
+    int32_t reserved;
+    int64_t* counters;          /* [4], elements 0..2 accumulated, or NULL */
+    uint8_t* frame_flags;       /* [B] or NULL */
+    uint8_t* n_iter;            /* [B] or NULL */
+    int64_t* iter_hist;         /* [T] accumulated, or NULL */
+} ldpc_es_outputs;
+
+/* ldpc_decode with the early-stop rule above (no reference counterpart). */
+int ldpc_decode_es(ldpc_ctx* ctx, const float* llr_dev, int64_t B, const ldpc_decode_params* params,
+                   const ldpc_es_outputs* es_outputs, void* stream);
+/* ldpc_decode_awgn with the early-stop rule above (no reference counterpart): identical to
+   ldpc_channel_awgn followed by ldpc_decode_es. */
+int ldpc_decode_awgn_es(ldpc_ctx* ctx, int64_t B, const ldpc_decode_params* params,
+                        const ldpc_channel_params* channel, const ldpc_es_outputs* es_outputs,
+                        void* stream);
+/* Whether ldpc_decode_es serves these parameters on this context: 1, 0, or a negative status
+   (no reference counterpart). */
+int ldpc_es_supported(const ldpc_ctx* ctx, const ldpc_decode_params* params);
+
 /* The LLR rows ldpc_channel_awgn(B, ..., offset) would write at batch rows idx_dev[0..n) (each
    index < B, any order), into rows_dev[n][n_vars]: the same values bit for bit, generated for
    those codewords only -- the uncorrected-word sweep regenerates the few failing frames' rows

@@ -21,7 +21,10 @@ extern "C" {
  * (the round-4 fault), so a test can see the check catch it.  flags bit 1
  * (LDPC_BOUNDS_BIG_TABLES): take the in-prologue channel's sampler tables to be 4 bytes longer
  * than the LDS region the plan lends them (the slot region; bsc: the SGN region), wherever the
- * plan passes the test that lets that build run; the check then reports "channel tables".  Only
+ * plan passes the test that lets that build run; the check then reports "channel tables".
+ * flags bit 2 (LDPC_BOUNDS_ES): also check the plans of the early-stop instances (ldpc_decode_es),
+ * with their hard-decision / syndrome reads on and their syndrome words in LDS; without it the
+ * plans checked, and the count returned, are those of the decodes without the mode.  Only
  * the checks read the flags, no kernel or launch path does.  Returns the number of plans
  * checked (>= 0) or a negative status; *violations = out-of-bounds reads found, msg = the
  * first one ("" if none). */

@@ -74,6 +74,7 @@ struct BsPlan {
     int inst = -1, nw = 0, cn_lanes = 0, arows = 1, bcols = 1;
     uint32_t off_slots = 0, off_pad = 0, off_zero = 0, off_red = 0, off_alut = 0, off_blut = 0, off_hdz = 0,
              off_ch = 0, off_hdl = 0;
+    uint32_t off_esu = 0;          // ES instances: the T syndrome words (in the RED region)
     int cn_dmin = 0;
     bool ucn = false;
     bool colalign = false;         // variable lanes: each column on a half-wave of its own
@@ -208,11 +209,18 @@ static BsPlan plan_inst(const DevGraph& g, int i, bool ucn, float clip, int min_
     // with ds_read_b128 (T = 50 unrounded put them 8 B off: C3 17.8 -> 24.4 ms, C5 61 -> 81 ms)
     // and the FLORW words the variable phases OR their frame-error words into
     o += 64 + (((size_t)4 * T + 15) & ~(size_t)15) + 4 * FLORW;
+    if (k.ES) {                    // + the T syndrome words of the early-stop builds, rounded alike
+        p.off_esu = (uint32_t)o;
+        o += ((size_t)4 * T + 15) & ~(size_t)15;
+    }
     p.off_alut = (uint32_t)o;
     o += (size_t)2 * (k.UCN ? 2 : 1) * p.arows * LUT_W * 4;
     p.off_blut = (uint32_t)o;
     o += (size_t)2 * p.bcols * BLUT_W * 4;
-    if (k.PK && k.CPL == 1 && o > 65535) return p;  // 16-bit alpha-table addresses (PKG)
+    // 16-bit alpha-table addresses (PKG).  (The ES instances: the packed address is a check lane's
+    // alpha-table base in the first buffer, the only one that has to stay below 64 KB -- wman's
+    // per-row tables of a UCN-compiled instance end above it)
+    if (k.PK && k.CPL == 1 && (k.ES ? (size_t)p.off_alut + (size_t)p.arows * LUT_W * 4 : o) > 65535) return p;
     if (k.CPL == 1) {                              // the check lanes' slot-base words
         p.off_ch = (uint32_t)o;
         o += (size_t)4 * 64 * p.nw;
@@ -228,7 +236,9 @@ static BsPlan plan_inst(const DevGraph& g, int i, bool ucn, float clip, int min_
     return p;
 }
 
-BsPlan bs_plan(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T) {
+// es: the plan of an early-stop request, which only the ES instances serve; every other
+// request never takes one of them
+BsPlan bs_plan(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T, bool es = false) {
     BsPlan p;
     const char* e = getenv("LDPC_BS");
     if (e && atoi(e) == 0) return p;
@@ -243,6 +253,12 @@ BsPlan bs_plan(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float cli
     for (int i = 0; i < h.M; ++i) min_cdeg = std::min(min_cdeg, h.row_ptr[i + 1] - h.row_ptr[i]);
     if (min_cdeg < 2) return p;                                   // ("no other edge" rule unneeded)
     for (int i = 0; i < kBsNInst; ++i) {
+        if (kBsInst[i].ES != es) continue;
+        if (es) {
+            BsPlan q = plan_inst(g, i, ucn, clip, min_cdeg, mode, T);
+            if (q.ok) return q;
+            continue;
+        }
         if (want_lpc != 0 && want_lpc != kBsInst[i].LPC) continue;
         if (want_inst >= 0 && want_inst != i) continue;
         BsPlan q = plan_inst(g, i, ucn, clip, min_cdeg, mode, T);
@@ -697,8 +713,14 @@ static BsHostTables bs_host_tables(const DevGraph& g, const BsPlan& p) {
     t.chd.swap(chd);
     return t;
 }
-static int bs_graph_tables(const DevGraph& g, const BsPlan& p, FusedWorkspace& ws, hipStream_t s) {
-    if (ws.bs_graph) return LDPC_OK;
+// (graph, inst: the context's cache of them -- ws.bs_graph / bs_graph_inst, or the early-stop
+// instances' own pair, so alternating decodes of both kinds rebuild nothing)
+static int bs_graph_tables(const DevGraph& g, const BsPlan& p, void*& graph, int& inst, hipStream_t s) {
+    if (graph && inst != p.inst) {
+        (void)hipFree(graph);
+        graph = nullptr;
+    }
+    if (graph) return LDPC_OK;
     BsHostTables t = bs_host_tables(g, p);
     const std::vector<uint32_t>& vn = t.vn;
     const std::vector<int32_t>& wdeg = t.wdeg;
@@ -723,8 +745,8 @@ static int bs_graph_tables(const DevGraph& g, const BsPlan& p, FusedWorkspace& w
         (void)hipFree(d);
         return LDPC_ERR_HIP;
     }
-    ws.bs_graph = d;
-    ws.bs_graph_inst = p.inst;
+    graph = d;
+    inst = p.inst;
     return LDPC_OK;
 }
 
@@ -735,15 +757,13 @@ bool bs_q8_ok(const DevGraph& g, int mode, bool ucn, float clip, int T, bool has
     return (!has_short || p.cu > 0.f) && q8_tab_fits(p);
 }
 
-int bs_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode,
-              bool ucn, int64_t* counters, uint8_t* flags, uint32_t* bad, uint32_t* hdx, hipStream_t s) {
-    const BsPlan p = bs_plan(g, mode, ucn, false, b.clip, b.T);
-    if (!p.ok) return bsc_decode(g, b, ws, llr, mode, ucn, counters, flags, bad, hdx, s);
-    if (ws.bs_graph && ws.bs_graph_inst != p.inst) {
-        (void)hipFree(ws.bs_graph);
-        ws.bs_graph = nullptr;
-    }
-    int st = bs_graph_tables(g, p, ws, s);
+// one launch of plan p; es: the early-stop outputs (an ES instance's plan), else null
+struct EsOut { uint8_t* n_iter; int64_t* iter_hist; };
+static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const BsPlan& p, const float* llr, int mode,
+                  bool ucn, int64_t* counters, uint8_t* flags, uint32_t* bad, uint32_t* hdx, const EsOut* es,
+                  hipStream_t s) {
+    int st = es ? bs_graph_tables(g, p, ws.bs_es_graph, ws.bs_es_graph_inst, s)
+                : bs_graph_tables(g, p, ws.bs_graph, ws.bs_graph_inst, s);
     if (st != LDPC_OK) return st;
     const BsInst& k = kBsInst[p.inst];
     const float step = mode_step_bs(mode);
@@ -753,8 +773,14 @@ int bs_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float*
     if (st != LDPC_OK) return st;
     const int DV = k.DV;
     const int VNW = (k.PK ? (DV + 1) / 2 : DV) + 1;
-    const uint32_t* gt = reinterpret_cast<const uint32_t*>(ws.bs_graph);
-    BsArgs a{};
+    const uint32_t* gt = reinterpret_cast<const uint32_t*>(es ? ws.bs_es_graph : ws.bs_graph);
+    // (BsArgs, and the early-stop builds' additions: an ES instance's launch reads them, every
+    // other launch takes the BsArgs base alone)
+    BsArgsEs a{};
+    if (es) {
+        a.n_iter = es->n_iter;
+        a.iter_hist = es->iter_hist;
+    }
     a.llr = llr;
     if (b.q8) {                          // the in-prologue channel (ldpc_decode_awgn)
         const AwgnParams& g8 = *reinterpret_cast<const AwgnParams*>(b.gen8);
@@ -801,7 +827,7 @@ int bs_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float*
     a.counters = counters;
     a.flags = flags;
     a.bad = bad;
-    a.iter_wrong = b.iter_wrong;
+    a.iter_wrong = es ? nullptr : b.iter_wrong;
     a.hdx = hdx;
     bs_stagger(k.VPL > 1 || k.CPL > 1, &a.stagger, &a.stagger_n);
     a.off_slots = p.off_slots;
@@ -857,6 +883,56 @@ int bs_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float*
 #endif
 }
 
+int bs_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode,
+              bool ucn, int64_t* counters, uint8_t* flags, uint32_t* bad, uint32_t* hdx, hipStream_t s) {
+    const BsPlan p = bs_plan(g, mode, ucn, false, b.clip, b.T);
+    if (!p.ok) return bsc_decode(g, b, ws, llr, mode, ucn, counters, flags, bad, hdx, s);
+    return bs_run(g, b, ws, p, llr, mode, ucn, counters, flags, bad, hdx, nullptr, s);
+}
+
+// ---- early stop ---------------------------------------------------------------
+bool bs_es_supported(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T) {
+    return bs_plan(g, mode, ucn, per_edge_w, clip, T, true).ok;
+}
+bool bs_es_q8_ok(const DevGraph& g, int mode, bool ucn, float clip, int T, bool has_short) {
+    const BsPlan p = bs_plan(g, mode, ucn, false, clip, T, true);
+    return p.ok && (!has_short || p.cu > 0.f) && q8_tab_fits(p);
+}
+const char* bs_es_kernel_name(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T) {
+    static thread_local char buf[64];
+    const BsPlan p = bs_plan(g, mode, ucn, per_edge_w, clip, T, true);
+    if (!p.ok) return "";
+    const BsInst& k = kBsInst[p.inst];
+    snprintf(buf, sizeof(buf), "bsl[p32,w%d,d%d,v%d,l%d%s,es]", p.nw, k.D, k.DV, k.LPC, p.ucn ? ",ucn" : "");
+    return buf;
+}
+// the early-stop decode of b.B codewords (LLRs at llr, or the in-prologue channel b.q8 / b.gen8):
+// counters [0..2], frame flags, n_iter [B] and iter_hist [T], each or null.  Packs with an LLR off
+// the grid are marked (flags 0x80, n_iter 0), not decoded.  LDPC_ERR_UNSUPPORTED: no ES instance
+// serves the request; nothing was launched.
+int bs_decode_es(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode, bool ucn,
+                 int ntiles_max, int64_t* counters, uint8_t* flags, uint8_t* n_iter, int64_t* iter_hist,
+                 hipStream_t s) {
+    const BsPlan p = bs_plan(g, mode, ucn, false, b.clip, b.T, true);
+    if (!p.ok) return LDPC_ERR_UNSUPPORTED;
+    if (b.q8 && !bs_es_q8_ok(g, mode, ucn, b.clip, b.T, reinterpret_cast<const AwgnParams*>(b.gen8)->ss > 0))
+        return LDPC_ERR_UNSUPPORTED;
+    const int64_t npk = (b.B + 31) / 32;
+    if (npk > ws.bs_bad_n) {             // (the kernel's per-pack off-grid word, as bs_decode's)
+        if (ws.bs_bad) (void)hipFree(ws.bs_bad);
+        ws.bs_bad = nullptr;
+        ws.bs_bad_n = 0;
+        const int64_t n = std::max<int64_t>(npk, (int64_t)ntiles_max * 8);
+        if (hipMalloc(reinterpret_cast<void**>(&ws.bs_bad), (size_t)n * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            return LDPC_ERR_OOM;
+        }
+        ws.bs_bad_n = n;
+    }
+    const EsOut es{n_iter, iter_hist};
+    return bs_run(g, b, ws, p, llr, mode, ucn, counters, flags, ws.bs_bad, nullptr, &es, s);
+}
+
 }  // namespace ldpc
 
 // ---- host-side bounds check of the bit-sliced kernel's reads (test infrastructure) -----------
@@ -903,7 +979,8 @@ static int bs_bounds_check(const DevGraph& g, const BsPlan& p, const BsHostTable
     const int EPL = (k.D + LPC - 1) / LPC, HDW = (EPL + 1) / 2, OB = 4 / LPC;
     const int VNA = k.PK ? (DV + 1) / 2 : DV, VNW = VNA + 1;
     const int NT = 64 * p.nw, nwv = p.nw, nv = g.n_vars, z = h.z;
-    const bool UCN = k.UCN, ucn = UCN && p.ucn;
+    // (an ES instance takes the hard decisions and syndromes whether or not UCN weights are set)
+    const bool UCN = k.UCN, ucn = UCN && (p.ucn || k.ES);
     const int AR = UCN ? 2 * p.arows : p.arows;
     const long long AL = (long long)AR * LUT_W, BL = (long long)p.bcols * BLUT_W;
     const long long lds = (long long)p.lds;
@@ -916,7 +993,14 @@ static int bs_bounds_check(const DevGraph& g, const BsPlan& p, const BsHostTable
                 p.inst, p.nw, (int)p.ucn, lds, p.off_slots, p.off_pad, p.off_alut, p.off_blut, p.off_ch, p.off_hdl);
     r.in("lds size", lds, (long long)BS_LDS_MAX + 1);
     if ((long long)t.vn.size() != (long long)VPL * NT * VNW) r.fail("vn_tab size", (long long)t.vn.size(), (long long)VPL * NT * VNW);
-    r.lds("RED", p.off_red, 4LL * (16 + ((T + 3) & ~3) + FLORW), 0, p.off_alut);
+    r.lds("RED", p.off_red, 4LL * (16 + ((T + 3) & ~3) + FLORW), 0, k.ES ? p.off_esu : p.off_alut);
+    if (k.ES) {                    // the T syndrome words, between the FLORW words and the tables
+        r.lds("syndrome words", p.off_esu, 4LL * T, p.off_red, p.off_alut);
+        r.apart("syndrome words / RED", p.off_esu, 4LL * T, p.off_red, 4LL * (16 + ((T + 3) & ~3) + FLORW));
+        // (the kernel addresses them from RED: RED[flor + FLORW + t])
+        if (p.off_esu != p.off_red + 4u * (uint32_t)(16 + ((T + 3) & ~3) + FLORW)) r.fail("syndrome words' offset", p.off_esu, p.off_red);
+        if (p.off_alut & 15) r.fail("alpha tables off 16 B", p.off_alut & 15, 1);
+    }
     r.lds("ALUT", p.off_alut, 4 * 2 * AL, 0, p.off_blut);
     r.lds("BLUT", p.off_blut, 4 * 2 * BL, 0, lds);
     r.lds("PAD+ZERO", p.off_pad, 2 * SLOT_B, p.off_slots, p.off_red);
@@ -1020,6 +1104,7 @@ static int bs_bounds_check(const DevGraph& g, const BsPlan& p, const BsHostTable
                 const long long ctab = p.off_alut + (long long)(p.arows > 1 ? ci : 0) * LUT_W * 4 + (long long)cj * OB * 64;
                 const long long last = ctab + 4LL * AL + (UCN ? (long long)p.arows * LUT_W * 4 : 0) + (OB - 1) * 64 + 3 * 16;
                 r.lds("alpha table", ctab, 16, p.off_alut, p.off_alut + 4 * 2 * AL);
+                if (k.PK && CPL == 1) r.in("packed alpha-table address", ctab, 65536);
                 r.lds("alpha table (odd t, alpha')", last, 16, p.off_alut, p.off_alut + 4 * 2 * AL);
             }
         }
@@ -1057,6 +1142,9 @@ extern "C" int ldpc_debug_bs_bounds(const int32_t* proto, int32_t M, int32_t N, 
     std::string first;
     for (int i = 0; i < kBsNInst; ++i)
         for (int u = 0; u < 2; ++u) {
+            // (the early-stop instances' plans with LDPC_BOUNDS_ES only: without it the checked
+            // plans are those of the decodes without the mode)
+            if (kBsInst[i].ES && !(flags & LDPC_BOUNDS_ES)) continue;
             const BsPlan p = plan_inst(g, i, u != 0, clip, min_cdeg, mode, T);
             if (!p.ok) continue;
             const BsHostTables t = bs_host_tables(g, p);

@@ -13,7 +13,7 @@ namespace bs {
 template <>
 int bs_launch<BS_INST>(const BsArgs& a, int npacks, int nw, size_t lds, hipStream_t s, bool q8, int grid,
                        int* resident) {
-    return launch_bs<BS_INST>(a, npacks, nw, lds, s, q8, grid, resident);
+    return launch_bs_any<BS_INST>(a, npacks, nw, lds, s, q8, grid, resident);
 }
 
 }  // namespace bs

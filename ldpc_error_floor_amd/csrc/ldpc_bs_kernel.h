@@ -53,7 +53,9 @@ constexpr size_t BS_LDS_MAX = 160 * 1024;
 // VPL / CPL = variables / 64-lane check chunks per lane, UCN / BIG = unsatisfied-check weights /
 // shortened bits supported, PK = 16-bit packed slot addresses, WPE = waves per SIMD (registers).
 // The multi-chunk instances (VPL / CPL > 1) run 16 waves.
-struct BsInst { int D, DV, LPC, VPL, CPL; bool UCN, BIG, PK; int WPE; };
+// ES: an early-stop-only instance: its builds carry the syndrome stop rule, and
+// bs_plan takes it for early-stop requests and never otherwise.
+struct BsInst { int D, DV, LPC, VPL, CPL; bool UCN, BIG, PK; int WPE; bool ES = false; };
 constexpr BsInst kBsInst[] = {
     {15, 6, 4, 1, 1, false, false, true, 8},     // wman (C2), LPC 4 measured 6.31 ms vs 6.73
     {16, 8, 4, 1, 1, false, false, true, 8},
@@ -64,6 +66,8 @@ constexpr BsInst kBsInst[] = {
     {10, 8, 2, 2, 2, true, true, false, 4},      // 5G BG2 (C4): 1,280 variables, 640 checks;
                                                  // 18.2 ms vs 21.2 for LPC 4 (CPL 3), same box
     {10, 8, 4, 2, 3, true, true, false, 4},      // LDPC_BS_LPC=4 A/B
+    {15, 6, 4, 1, 1, true, false, true, 6, true},   // wman, early stop (UCN-compiled: HD / syndromes)
+    {24, 4, 4, 1, 1, true, true, true, 6, true},    // 802.11n, early stop
 };
 constexpr int kBsNInst = sizeof(kBsInst) / sizeof(kBsInst[0]);
 
@@ -132,6 +136,22 @@ struct BsArgs {
                                  // barrier, 11 tables, 12 first variable phase; 15 packs), timing
                                  // diagnostics
 };
+
+// The early-stop builds' arguments (ES instances): BsArgs and what the mode adds, so the other
+// builds' kernel arguments stay as they are.
+struct BsArgsEs : BsArgs {
+    uint8_t* n_iter;             // [B] iterations run per codeword (0: pack off the grid), or null
+    int64_t* iter_hist;          // [T] += codewords with n_iter = t + 1, or null
+    // (LDS: the T syndrome words follow the FLORW words of the RED region, RED[flor + FLORW + t]:
+    // word t = OR over the checks of the syndrome of iteration t's hard decisions)
+};
+
+// the kernel's own arguments read from the kernel-argument segment (scalar loads): how the
+// early-stop statements reach their fields, also where the pack loop's units rename `a`
+template <class A>
+__device__ __forceinline__ const __attribute__((address_space(4))) A& kern_args() {
+    return *(const __attribute__((address_space(4))) A*)__builtin_amdgcn_kernarg_segment_ptr();
+}
 
 // bit-plane arithmetic (B3, the truth tables, add_b / set_b / sub_tv / abs_sat / lt4 / clamp6):
 // ldpc_bitplane.h
@@ -598,10 +618,17 @@ constexpr bool bs_loops(const BsInst& k) { return k.VPL == 1 && k.CPL == 1 && !k
 // Q8: the channel generated in the prologue (a.gen: ldpc_decode_awgn) instead of read as float
 // LLRs; a build of its own (a run-time branch moved the register allocation of the whole kernel: C3's
 // spills 5 -> 9 VGPRs)
-template <int D, int DV, int LPC, int VPL, int CPL, bool UCN, bool BIG, bool PK, int WPE, bool XP, int LB, bool Q8>
+// ES: the early-stop build (one-chunk UCN-compiled instances, one pack per
+// workgroup).  The hard decisions go to HD and the check phases take their syndromes at every
+// iteration; a pack leaves the T loop once each of its codewords has had a zero syndrome, and the
+// epilogue takes every codeword's outputs at its own first zero-syndrome iteration.
+template <int D, int DV, int LPC, int VPL, int CPL, bool UCN, bool BIG, bool PK, int WPE, bool XP, int LB, bool Q8,
+          bool ES = false>
 __global__ void __launch_bounds__(LB) __attribute__((amdgpu_waves_per_eu(WPE)))
-k_bs(BsArgs a) {
+k_bs(std::conditional_t<ES, BsArgsEs, BsArgs> a) {
     static_assert(LPC == 2 || LPC == 4, "lanes per check");
+    using KArgs = std::conditional_t<ES, BsArgsEs, BsArgs>;
+    static_assert(!ES || (UCN && VPL == 1 && CPL == 1 && !XP), "early stop: one-chunk UCN-compiled instances");
     constexpr int SB = (DV * QMAX + QMAX <= 127) ? 8 : 9;     // planes of S and of lw + S
     constexpr int EPL = (D + LPC - 1) / LPC;                     // edge slots per check lane
     constexpr bool SKIPM = CPL > 1;                              // chunk-wide padding skipped
@@ -749,6 +776,14 @@ k_bs(BsArgs a) {
     }
 #endif
     if (tid < FLORW) RED[flor + tid] = 0u;
+    // early stop: the done word (wave-uniform, every wave keeps its own copy: a codeword's bit is
+    // set once an iteration's hard decisions had a zero syndrome; the bits past the pack's
+    // codewords start set, so a ragged pack's padding never holds the pack back) and the T
+    // syndrome words, zeroed
+    [[maybe_unused]] uint32_t es_done = ~valid;
+    if constexpr (ES) {
+        for (int w = tid; w < a.T; w += NT) RED[flor + FLORW + w] = 0u;
+    }
     // (the barrier that orders these writes before the channel's flag updates: here when the
     // channel is generated from the sampler's tables; else after the first variable's LLR loads
     // are issued, so that it waits beside their HBM round trip, EBR)
@@ -860,6 +895,14 @@ k_bs(BsArgs a) {
     __syncthreads();
     BS_ST(10);
     if (RED[7]) {                              // off the grid: the v5 fixup decodes this pack
+        if constexpr (ES) {
+            // early stop: no fixup (v5 has no stop rule); the pack's frames are marked undecoded
+            // and enter neither the counters nor the histogram
+            if (tid < nvalid) {
+                if (a.flags) a.flags[b0 + tid] = 0x80;
+                if (kern_args<KArgs>().n_iter) kern_args<KArgs>().n_iter[b0 + tid] = 0;
+            }
+        }
         if (tid == 0) a.bad[BS_PK] = 1u;
         BS_NEXT_PACK;                          // (wave-uniform: every thread read the same word)
     }
@@ -1018,7 +1061,8 @@ k_bs(BsArgs a) {
                         for (int i = 0; i < SB - 1; ++i) c = B3(T_MAJ, S[i], i < 4 ? (cmu[i] ^ c_s) : c_s, c);
                         hd = B3(T_XNOR3, S[SB - 1], c_s, c);
                     }
-                    if (UCN && !last && v >= 0 && ucn_on(tb)) lds_put(hda, hd);   // HD[v] (Main_Functions.py:184-188)
+                    // (early stop: at every iteration, for the next check phase's syndromes)
+                    if (UCN && !last && v >= 0 && (ES || ucn_on(tb))) lds_put(hda, hd);   // HD[v] (Main_Functions.py:184-188)
                     hd &= valid;                                     // APP >= 0 -> hard decision 1
                     if constexpr (XP) {                              // iteration tb - 1's hard decisions
                         if (v >= 0) a.hdx[((size_t)(tb - 1) * (size_t)((a.B + 31) >> 5) + BS_PK) * nv + v] = hd;
@@ -1028,6 +1072,9 @@ k_bs(BsArgs a) {
                         wr |= hd;
                         if (last) {
                             apos |= hd & nz;
+                            // (early stop: the codewords not done before count at T - 1)
+                            if constexpr (ES) nb += (uint32_t)__popc(hd & ~es_done);
+                            else
                             nb += (uint32_t)__popc(hd);
                         }
                     }
@@ -1143,7 +1190,7 @@ k_bs(BsArgs a) {
 #pragma unroll
             // (the table holds the cn_lanes check lanes: a one-chunk instance's waves past them
             // read nothing -- their reads ran off the end of the allocation)
-            for (int p = 0; p < HDW; ++p) ghd[c][p] = (ucn && gchunk[c] >= 0 && ql < a.cn_lanes) ? a.cn_hd[(size_t)ql * HDW + p] : 0u;
+            for (int p = 0; p < HDW; ++p) ghd[c][p] = ((ES || ucn) && gchunk[c] >= 0 && ql < a.cn_lanes) ? a.cn_hd[(size_t)ql * HDW + p] : 0u;
         }
     }
     // the lane's real edge positions, one word for all its chunks (bit RB c + m: position m of
@@ -1291,7 +1338,9 @@ k_bs(BsArgs a) {
             PH("ck_syn", c);
             const bool ucn_t = ucn_on(t);
             if constexpr (UCN) {
-                if (ucn_t) {
+                // (early stop: check phase t > 0 takes the syndrome of iteration t - 1's hard
+                // decisions whether or not alpha' needs it)
+                if (ucn_t || (ES && t > 0)) {
                     // (the packed addresses made opaque per iteration: unpacked per use, not
                     // hoisted out of the T loop as EPL registers that the loop then spilled;
                     // HDL: read from LDS, through a lane index the loop cannot hoist)
@@ -1318,6 +1367,15 @@ k_bs(BsArgs a) {
                     }
                     syn ^= qperm<QP_X1>(syn);
                     if (LPC == 4) syn ^= qperm<QP_X2>(syn);
+                    if constexpr (ES) {
+                        // the codewords with an unsatisfied check, ORed into syndrome word t - 1
+                        if (t > 0) {
+                            const uint32_t wu = wave_or(syn);
+                            if (wu && BS_LANE_IS0)
+                                __hip_atomic_fetch_or(RED + flor + FLORW + (t - 1), wu,
+                                                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        }
+                    }
                 }
             }
             PH4("ck_min", c, Xs[EPL - 1]);
@@ -1417,6 +1475,28 @@ k_bs(BsArgs a) {
         BS_ST(0);
         __syncthreads();
         BS_ST(1);
+        if constexpr (ES) {
+            // ======== early stop ================================================================
+            // syndrome word t - 1 is complete (the barrier): the codewords newly done at iteration
+            // t - 1 are those with no unsatisfied check that were not done before.  Their bit
+            // errors are counted from HD, which still holds iteration t - 1's hard decisions; once
+            // every codeword is done the workgroup leaves the loop (every wave reads the same
+            // word: a workgroup-uniform branch; the barrier retired the async table copies).
+            if (t > 0) {
+                const uint32_t un = (uint32_t)__builtin_amdgcn_readfirstlane((int)RED[flor + FLORW + t - 1]);
+                const uint32_t nn = ~un & ~es_done;
+                es_done |= nn;
+                if (nn) {
+                    const int v = vv[0] >= 0 ? (vv[0] & 0xFFFF) : -1;
+                    uint32_t nb = 0u;
+                    if (v >= 0 && v < a.target_bits)
+                        nb = (uint32_t)__popc(lds_w(4u * ((uint32_t)vv[0] >> 16)) & nn);
+                    nb = wave_add(nb);
+                    if (nb && BS_LANE_IS0) atomicAdd(&RED[3], nb);
+                }
+                if (es_done == 0xFFFFFFFFu) break;
+            }
+        }
         // ======== variable nodes ================================================================
         if (PRIO == 2) __builtin_amdgcn_s_setprio(0);
         if (PRIO == 4) {                             // the waves of the heaviest variables first
@@ -1451,6 +1531,62 @@ k_bs(BsArgs a) {
 #else
     const int te = tid;
 #endif
+    if constexpr (ES) {
+        // early stop: each codeword's outputs at its own stop iteration -- the first t whose
+        // syndrome word has its bit clear, else T - 1 -- from the syndrome words and the
+        // per-iteration frame-error words (RED[16 + t]; iteration T - 1's is RED[0]); one lane of
+        // wave 0 per codeword.  (The words past the iteration the pack left the loop at are not
+        // used: every codeword has stopped by then.)
+        __syncthreads();                 // the bit counts of the waves that left the loop
+        if (wave == 0) {
+            const uint32_t* ESU = RED + flor + FLORW;
+            const int r = te & 31;
+            const bool on = te < nvalid;
+            int stop = a.T - 1;
+            uint32_t all = 1u, wl = 0u;
+            bool open = true;
+            for (int t = 0; t < a.T; ++t) {
+                const bool lastt = t == a.T - 1;
+                const uint32_t w = lastt ? RED[0] : RED[16 + t];
+                const uint32_t u = lastt ? 0u : ESU[t];
+                if (open) {
+                    wl = (w >> r) & 1u;
+                    all &= wl;
+                    if (!((u >> r) & 1u)) {
+                        stop = t;
+                        open = false;
+                    }
+                }
+            }
+            const unsigned long long mw = __builtin_amdgcn_ballot_w64(on && wl != 0u);
+            const unsigned long long ma = __builtin_amdgcn_ballot_w64(on && all != 0u);
+            if (on) {
+                if (e_flags) e_flags[b0 + te] = (uint8_t)(all | (wl << 1));
+                if (kern_args<KArgs>().n_iter) kern_args<KArgs>().n_iter[b0 + te] = (uint8_t)(stop + 1);
+            }
+            if (te == 0 && e_counters) {
+                unsigned long long* cc = reinterpret_cast<unsigned long long*>(e_counters);
+                const unsigned long long c0 = RED[3], c1 = __popcll(mw), c2 = __popcll(ma);
+                if (c0) atomicAdd(cc + 0, c0);
+                if (c1) atomicAdd(cc + 1, c1);
+                if (c2) atomicAdd(cc + 2, c2);
+            }
+            if (kern_args<KArgs>().iter_hist) {           // one atomic per distinct stop iteration of the pack
+                unsigned long long rem = __builtin_amdgcn_ballot_w64(on);
+                while (rem) {
+                    const int l = __builtin_ctzll(rem);
+                    const int ts = __builtin_amdgcn_readlane(stop, l);
+                    const unsigned long long m = __builtin_amdgcn_ballot_w64(on && stop == ts);
+                    if (te == l)
+                        atomicAdd(reinterpret_cast<unsigned long long*>(kern_args<KArgs>().iter_hist) + ts,
+                                  (unsigned long long)__popcll(m));
+                    rem &= ~m;
+                }
+            }
+        }
+    }
+    if constexpr (!ES) {
+    // (the body keeps the indentation it had before the early-stop builds)
     if (te == 0) {
         const uint32_t wl = RED[0] & valid;
         const uint32_t all = RED[1] & RED[0] & valid;
@@ -1475,6 +1611,7 @@ k_bs(BsArgs a) {
         if (e_iter_wrong)                   // [T][packs]: iteration t's frame-error word
             for (int t = te; t < a.T; t += NT)
                 e_iter_wrong[(size_t)t * (size_t)((e_B + 31) >> 5) + BS_PK] = RED[16 + t] & valid;
+    }
     }
     BS_ST(5);
 #if BS_LOOP_TU
@@ -1550,6 +1687,35 @@ int launch_bs(const BsArgs& a, int npacks, int nw, size_t lds, hipStream_t s, bo
     if (a.hdx) return q8 ? LDPC_ERR_UNSUPPORTED : launch_bs_x<I, true, false>(a, npacks, nw, lds, s, grid, resident + 1);
     return q8 ? launch_bs_x<I, false, true>(a, npacks, nw, lds, s, grid, resident + 2)
               : launch_bs_x<I, false, false>(a, npacks, nw, lds, s, grid, resident);
+}
+
+// the early-stop builds of an ES instance (float LLRs, or the in-prologue channel): one workgroup
+// per pack, no pack loop (packs end at different times) and no export build
+template <int I, bool Q8>
+int launch_bs_es_x(const BsArgsEs& a, int npacks, int nw, size_t lds, hipStream_t s) {
+    constexpr BsInst k = kBsInst[I];
+    static_assert(k.ES && !bs_loops(k), "an early-stop instance");
+    auto* fn = &k_bs<k.D, k.DV, k.LPC, k.VPL, k.CPL, k.UCN, k.BIG, k.PK, k.WPE, false, 1024, Q8, true>;
+    static bool attr = false;
+    if (!attr) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)BS_LDS_MAX);
+        attr = true;
+    }
+    hipLaunchKernelGGL(fn, dim3(npacks), dim3(64 * nw), lds, s, a);
+    return hipGetLastError() == hipSuccess ? LDPC_OK : LDPC_ERR_HIP;
+}
+// instance I's launch: an ES instance is handed the early-stop arguments (BsArgsEs, passed as
+// their BsArgs base) and has no other build; the others never see them
+template <int I>
+int launch_bs_any(const BsArgs& a, int npacks, int nw, size_t lds, hipStream_t s, bool q8, int grid, int* resident) {
+    if constexpr (kBsInst[I].ES) {
+        if (a.hdx) return LDPC_ERR_UNSUPPORTED;
+        const BsArgsEs& ae = static_cast<const BsArgsEs&>(a);
+        return q8 ? launch_bs_es_x<I, true>(ae, npacks, nw, lds, s) : launch_bs_es_x<I, false>(ae, npacks, nw, lds, s);
+    } else {
+        return launch_bs<I>(a, npacks, nw, lds, s, q8, grid, resident);
+    }
 }
 
 // per-instance translation units (ldpc_bs_inst.hip, -DBS_INST=i)

@@ -428,6 +428,56 @@ static bool q8_serves(const ldpc_ctx* c, const ldpc_decode_params* p, bool has_s
                        g->d_alpha_ucn != nullptr, g->per_edge_w != 0, has_short);
 }
 
+// The level sampler's tables of channel `a` (awgn_gen_table) in c->gen_tab, for a bit-sliced
+// decode with the in-prologue channel on `stream`; uploaded when the channel parameters change.
+static int ensure_gen_tab(ldpc_ctx* c, const AwgnParams& a, void* stream) {
+    if (!c->gen_tab) {
+        if (hipMalloc(reinterpret_cast<void**>(&c->gen_tab), sizeof(c->gen_host)) != hipSuccess) {
+            (void)hipGetLastError();
+            return LDPC_ERR_OOM;
+        }
+        c->gen_valid = false;
+    }
+    uint32_t tab[AWGN_TAB_W];
+    awgn_gen_table(a, tab);
+    if (!c->gen_done && hipEventCreateWithFlags(&c->gen_done, hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError();
+        c->gen_done = nullptr;
+        return LDPC_ERR_HIP;
+    }
+    if (!c->gen_valid || std::memcmp(tab, c->gen_host, sizeof(tab)) != 0) {
+        // a decode still reading the previous tables may run on another stream: wait for the
+        // last one that used them (gen_done) before the copy overwrites them; the stream wait
+        // keeps the host copy stable until the transfer has read it
+        if (c->gen_pending && hipEventSynchronize(c->gen_done) != hipSuccess) return LDPC_ERR_HIP;
+        c->gen_pending = false;
+        std::memcpy(c->gen_host, tab, sizeof(tab));
+        c->gen_valid = false;
+        if (hipMemcpyAsync(c->gen_tab, c->gen_host, sizeof(tab), hipMemcpyHostToDevice,
+                           reinterpret_cast<hipStream_t>(stream)) != hipSuccess ||
+            hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)) != hipSuccess)
+            return LDPC_ERR_HIP;
+        c->gen_valid = true;
+    }
+    return LDPC_OK;
+}
+// the context's float LLR buffer ([B_max][n_vars]) for decodes whose kernel reads its LLRs
+static int ensure_llr_scratch(ldpc_ctx* c) {
+    const ldpc_graph* g = c->g;
+    const int64_t n = c->B_max * (int64_t)g->h.N * g->h.z;
+    if (c->llr_scratch_n >= n) return LDPC_OK;
+    DeviceGuard dg(g->device);
+    if (c->llr_scratch) (void)hipFree(c->llr_scratch);
+    c->llr_scratch = nullptr;
+    c->llr_scratch_n = 0;
+    if (hipMalloc(reinterpret_cast<void**>(&c->llr_scratch), (size_t)n * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        return LDPC_ERR_OOM;
+    }
+    c->llr_scratch_n = n;
+    return LDPC_OK;
+}
+
 int ldpc_awgn_in_kernel(const ldpc_ctx* c, const ldpc_decode_params* p, int32_t has_short, int32_t app) {
     if (!c || !p) return LDPC_ERR_ARG;
     const ldpc_graph* g = c->g;
@@ -462,34 +512,8 @@ int ldpc_decode_awgn(ldpc_ctx* c, int64_t B, const ldpc_decode_params* p,
     // which reads its LLRs)
     if ((!o || (!o->app_all && !o->hard_bits && !o->synd_bits)) && q8_serves(c, p, ch->short_start > 0)) {
         DeviceGuard dg(g->device);
-        if (!c->gen_tab) {
-            if (hipMalloc(reinterpret_cast<void**>(&c->gen_tab), sizeof(c->gen_host)) != hipSuccess) {
-                (void)hipGetLastError();
-                return LDPC_ERR_OOM;
-            }
-            c->gen_valid = false;
-        }
-        uint32_t tab[AWGN_TAB_W];
-        awgn_gen_table(a, tab);
-        if (!c->gen_done && hipEventCreateWithFlags(&c->gen_done, hipEventDisableTiming) != hipSuccess) {
-            (void)hipGetLastError();
-            c->gen_done = nullptr;
-            return LDPC_ERR_HIP;
-        }
-        if (!c->gen_valid || std::memcmp(tab, c->gen_host, sizeof(tab)) != 0) {
-            // a decode still reading the previous tables may run on another stream: wait for the
-            // last one that used them (gen_done) before the copy overwrites them; the stream wait
-            // keeps the host copy stable until the transfer has read it
-            if (c->gen_pending && hipEventSynchronize(c->gen_done) != hipSuccess) return LDPC_ERR_HIP;
-            c->gen_pending = false;
-            std::memcpy(c->gen_host, tab, sizeof(tab));
-            c->gen_valid = false;
-            if (hipMemcpyAsync(c->gen_tab, c->gen_host, sizeof(tab), hipMemcpyHostToDevice,
-                               reinterpret_cast<hipStream_t>(stream)) != hipSuccess ||
-                hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)) != hipSuccess)
-                return LDPC_ERR_HIP;
-            c->gen_valid = true;
-        }
+        st = ensure_gen_tab(c, a, stream);
+        if (st != LDPC_OK) return st;
         st = decode_impl(c, nullptr, B, p, o, stream, nullptr, c->gen_tab, &a);
         if (st == LDPC_OK) {
             if (hipEventRecord(c->gen_done, reinterpret_cast<hipStream_t>(stream)) != hipSuccess) return LDPC_ERR_HIP;
@@ -498,18 +522,8 @@ int ldpc_decode_awgn(ldpc_ctx* c, int64_t B, const ldpc_decode_params* p,
         if (st != LDPC_ERR_UNSUPPORTED) return st;
     }
     // this kernel reads its LLRs: generate them into the context's buffer, then decode
-    const int64_t n = c->B_max * (int64_t)g->h.N * g->h.z;
-    if (c->llr_scratch_n < n) {
-        DeviceGuard dg(g->device);
-        if (c->llr_scratch) (void)hipFree(c->llr_scratch);
-        c->llr_scratch = nullptr;
-        c->llr_scratch_n = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&c->llr_scratch), (size_t)n * sizeof(float)) != hipSuccess) {
-            (void)hipGetLastError();
-            return LDPC_ERR_OOM;
-        }
-        c->llr_scratch_n = n;
-    }
+    st = ensure_llr_scratch(c);
+    if (st != LDPC_OK) return st;
     {
         DeviceGuard dg(g->device);
         st = ldpc_channel_awgn(c->llr_scratch, B, g->h.N * g->h.z, ch->sigma, ch->seed, ch->offset,
@@ -696,6 +710,104 @@ static int decode_impl(ldpc_ctx* c, const float* llr_dev, int64_t B, const ldpc_
         }
     }
     return hipGetLastError() == hipSuccess ? LDPC_OK : LDPC_ERR_HIP;
+}
+
+// ---- early stop (include/ldpc_nms.h) ------------------------------------------
+// the request's mode when an early-stop instance serves it, LDPC_ERR_UNSUPPORTED when none does,
+// or the status of a bad request (no device call)
+static int es_request(const ldpc_ctx* c, int64_t B, const ldpc_decode_params* p, int* mode) {
+    const ldpc_graph* g = c->g;
+    if (!g->d_alpha || !g->d_beta) return LDPC_ERR_STATE;
+    const int chk = host::check_decode(g->h, B, c->B_max, c->T_max, g->T_w, p, mode);
+    if (chk != LDPC_OK) return chk;
+    if (p->kernel != LDPC_KERNEL_AUTO && p->kernel != LDPC_KERNEL_FUSED)
+        return p->kernel == LDPC_KERNEL_FLOOD ? LDPC_ERR_UNSUPPORTED : LDPC_ERR_ARG;
+    if (p->decoding_type != LDPC_DEC_QMS || g->per_edge_w ||
+        !bs_es_supported(g->dev, *mode, g->d_alpha_ucn != nullptr, false, p->clip_llr, p->T))
+        return LDPC_ERR_UNSUPPORTED;
+    return LDPC_OK;
+}
+
+int ldpc_es_supported(const ldpc_ctx* c, const ldpc_decode_params* p) {
+    if (!c || !p) return LDPC_ERR_ARG;
+    int mode = -1;
+    const int st = es_request(c, 1, p, &mode);
+    return st == LDPC_OK ? 1 : st == LDPC_ERR_UNSUPPORTED ? 0 : st;
+}
+
+static int decode_es_impl(ldpc_ctx* c, const float* llr_dev, int64_t B, const ldpc_decode_params* p,
+                          const ldpc_es_outputs* o, void* stream, const uint32_t* q8, const AwgnParams* gen8) {
+    int mode = -1;
+    const int rq = es_request(c, B, p, &mode);
+    if (rq != LDPC_OK) return rq;
+    ldpc_graph* g = c->g;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    DeviceGuard dg(g->device);
+    const bool ucn = g->d_alpha_ucn != nullptr;
+    Bufs b{};
+    b.B = B;
+    b.ntiles = (int)((B + TILE - 1) / TILE);
+    b.T = p->T;
+    b.n_vars = g->h.N * g->h.z;
+    b.target_bits = p->target_bits;
+    b.clip = p->clip_llr;
+    b.alpha = g->d_alpha;
+    b.alpha_ucn = g->d_alpha_ucn;
+    b.beta = g->d_beta;
+    b.count = 1;
+    b.q8 = q8;
+    b.gen8 = gen8;
+    const int st = bs_decode_es(g->dev, b, c->fused, llr_dev, mode, ucn, c->ntiles_max, o->counters,
+                                o->frame_flags, o->n_iter, o->iter_hist, s);
+    if (st != LDPC_OK) return st;
+    std::snprintf(c->last_kernel, sizeof(c->last_kernel), "%s%s",
+                  bs_es_kernel_name(g->dev, mode, ucn, false, p->clip_llr, p->T), q8 ? "+gen" : "");
+    return hipGetLastError() == hipSuccess ? LDPC_OK : LDPC_ERR_HIP;
+}
+
+int ldpc_decode_es(ldpc_ctx* c, const float* llr_dev, int64_t B, const ldpc_decode_params* p,
+                   const ldpc_es_outputs* o, void* stream) {
+    if (!c || !llr_dev || !p || !o || o->size != (int32_t)sizeof(ldpc_es_outputs)) return LDPC_ERR_ARG;
+    return decode_es_impl(c, llr_dev, B, p, o, stream, nullptr, nullptr);
+}
+
+int ldpc_decode_awgn_es(ldpc_ctx* c, int64_t B, const ldpc_decode_params* p, const ldpc_channel_params* ch,
+                        const ldpc_es_outputs* o, void* stream) {
+    if (!c || !p || !ch || !o || o->size != (int32_t)sizeof(ldpc_es_outputs) || !(ch->sigma > 0.0) ||
+        ch->offset < 0)
+        return LDPC_ERR_ARG;
+    int mode = -1;
+    int st = es_request(c, B, p, &mode);
+    if (st != LDPC_OK) return st;
+    ldpc_graph* g = c->g;
+    const AwgnParams a = make_awgn(ch->sigma, ch->seed, ch->offset, p->decoding_type, p->q_bit,
+                                   ch->punct_start, ch->punct_end, ch->short_start, ch->short_end,
+                                   p->clip_llr);
+    static const bool q8_on = [] { const char* e = getenv("LDPC_AWGN_Q8"); return !(e && atoi(e) == 0); }();
+    if (q8_on && bs_es_q8_ok(g->dev, mode, g->d_alpha_ucn != nullptr, p->clip_llr, p->T, ch->short_start > 0)) {
+        {
+            DeviceGuard dg(g->device);
+            st = ensure_gen_tab(c, a, stream);
+        }
+        if (st != LDPC_OK) return st;
+        st = decode_es_impl(c, nullptr, B, p, o, stream, c->gen_tab, &a);
+        if (st == LDPC_OK) {
+            if (hipEventRecord(c->gen_done, reinterpret_cast<hipStream_t>(stream)) != hipSuccess) return LDPC_ERR_HIP;
+            c->gen_pending = true;
+        }
+        return st;
+    }
+    // the channel kernel writes float LLRs into the context's buffer first
+    st = ensure_llr_scratch(c);
+    if (st != LDPC_OK) return st;
+    {
+        DeviceGuard dg(g->device);
+        st = ldpc_channel_awgn(c->llr_scratch, B, g->h.N * g->h.z, ch->sigma, ch->seed, ch->offset,
+                               p->decoding_type, p->q_bit, ch->punct_start, ch->punct_end,
+                               ch->short_start, ch->short_end, p->clip_llr, stream);
+    }
+    if (st != LDPC_OK) return st;
+    return decode_es_impl(c, c->llr_scratch, B, p, o, stream, nullptr, nullptr);
 }
 
 int ldpc_ctx_last_kernel(const ldpc_ctx* c, char* name, int32_t name_len) {

@@ -13,6 +13,8 @@ struct FusedWorkspace {
     size_t tables_bytes = 0;
     void* bs_graph = nullptr;      // bit-sliced kernel: graph tables (built once per context)
     int bs_graph_inst = -1;        // the kernel instance they were built for
+    void* bs_es_graph = nullptr;   // the same for the early-stop instances (a pair of their own:
+    int bs_es_graph_inst = -1;     // alternating decodes of both kinds rebuild neither)
     void* bs_lut = nullptr;        // bit-sliced kernel: per-decode weight tables
     size_t bs_lut_bytes = 0;
     uint32_t* bs_bad = nullptr;    // [packs] 1: pack decoded by the v5 fixup
@@ -70,9 +72,18 @@ bool bs_q8_ok(const DevGraph& g, int mode, bool ucn, float clip, int T, bool has
 bool bsc_q8_ok(const DevGraph& g, int mode, bool ucn, float clip, int T, bool has_short);
 // host-side bounds check of the bsc plan (test infrastructure, ldpc_debug_bs_bounds), and the
 // flags of that check (include/ldpc_nms_debug.h): no kernel or launch path reads them
-enum { LDPC_BOUNDS_PRE_GUARD = 1, LDPC_BOUNDS_BIG_TABLES = 2 };
+enum { LDPC_BOUNDS_PRE_GUARD = 1, LDPC_BOUNDS_BIG_TABLES = 2, LDPC_BOUNDS_ES = 4 };
 int bsc_debug_bounds(const DevGraph& g, int mode, float clip, int T, int flags, int& violations,
                      std::string& first);
+// early stop (ldpc_decode_es): the bit-sliced kernel's ES instances serve the request;
+// their decode (counters [0..2], frame flags, n_iter [B], iter_hist [T], each or null; b.q8 / gen8:
+// the in-prologue channel, when bs_es_q8_ok) and its kernel name ("bsl[...,es]")
+bool bs_es_supported(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T);
+bool bs_es_q8_ok(const DevGraph& g, int mode, bool ucn, float clip, int T, bool has_short);
+const char* bs_es_kernel_name(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T);
+int bs_decode_es(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode, bool ucn,
+                 int ntiles_max, int64_t* counters, uint8_t* flags, uint8_t* n_iter, int64_t* iter_hist,
+                 hipStream_t s);
 // (fused_decode with it: the bit-sliced kernel or LDPC_ERR_UNSUPPORTED)
 bool fused_q8_ok(const DevGraph& g, int mode, int T, float clip, bool ucn, bool per_edge_w, bool has_short);
 // a decode with an in-kernel generator (Bufs::awgn) runs the v5 kernel's prologue channel

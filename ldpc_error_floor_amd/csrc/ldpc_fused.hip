@@ -182,6 +182,8 @@ void fused_free(FusedWorkspace& ws) {
     ws.tables_bytes = 0;
     if (ws.bs_graph) (void)hipFree(ws.bs_graph);
     ws.bs_graph = nullptr;
+    if (ws.bs_es_graph) (void)hipFree(ws.bs_es_graph);
+    ws.bs_es_graph = nullptr;
     if (ws.bs_lut) (void)hipFree(ws.bs_lut);
     ws.bs_lut = nullptr;
     ws.bs_lut_bytes = 0;

@@ -33,6 +33,9 @@ class DecodeResult:
     flags: Optional["object"] = None        # torch uint8 [B]
     iter_wrong: Optional["object"] = None   # torch int32 [T, ceil(B/32)]: bit b%32 of word
                                             # (t, b//32) = frame b wrong at iteration t
+    n_iter: Optional["object"] = None       # early stop: torch uint8 [B], iterations run (0: the
+                                            # frame's pack held an off-grid LLR and was not decoded)
+    iter_hist: Optional["object"] = None    # early stop: torch int64 [T], frames with n_iter == t+1
 
     def frame_errors(self, B: int) -> np.ndarray:
         """``iter_wrong`` unpacked on the host: bool [T, B] (calc_ber_fer's per-iteration frame
@@ -136,18 +139,107 @@ class NMSDecoder:
             raise ValueError(f"llr has {llr.shape[1]} bits per codeword, graph has {self.n_vars}")
         return llr
 
-    def decode(self, llr, T: Optional[int] = None, app: bool = True, hard: bool = False,
+    def supports_early_stop(self, T=None, kernel=None) -> bool:
+        """Whether ``decode(..., early_stop=True)`` is served for this decoder
+        (``ldpc_es_supported``): a QMS grid with q in {5, -5, 4, 3}, no per-edge check weights, kernel
+        auto or fused, and a graph that an early-stop instance of the bit-sliced kernel fits."""
+        T = self.T if T is None else int(T)
+        if T > self.T:
+            return False
+        ctx = self._ensure_ctx(1, T)
+        return bool(self._ext.es_supported(ctx, T, self.decoding_type, self.q_bit, self.target_bits,
+                                           KERNELS[kernel or self.kernel], self.clip))
+
+    def _es_outputs(self, res, B, T, counters, flags, n_iter, iter_hist):
+        """The early-stop decode's output tensors into ``res`` (caller-owned ones checked)."""
+        torch = self._torch
+        dev = self.device
+        if counters is True:
+            counters = torch.zeros(4, dtype=torch.int64, device=dev)
+        if counters is not None:
+            if counters.dtype != torch.int64 or counters.numel() < 4 or counters.device != dev:
+                raise ValueError("counters must be an int64[4] tensor on the decoder's device")
+            res.counters = counters
+        if isinstance(flags, torch.Tensor):
+            if flags.dtype != torch.uint8 or flags.device != dev or flags.numel() < B:
+                raise ValueError("flags tensor must be uint8 on the decoder's device, >= B long")
+            res.flags = flags
+        elif flags:
+            res.flags = torch.empty(B, dtype=torch.uint8, device=dev)
+        if n_iter:
+            res.n_iter = torch.empty(B, dtype=torch.uint8, device=dev)
+        if iter_hist is True:
+            iter_hist = torch.zeros(T, dtype=torch.int64, device=dev)
+        if iter_hist is not None and iter_hist is not False:
+            if (not isinstance(iter_hist, torch.Tensor) or iter_hist.dtype != torch.int64 or
+                    iter_hist.numel() < T or iter_hist.device != dev or not iter_hist.is_contiguous()):
+                raise ValueError("iter_hist must be a contiguous int64[T] tensor on the decoder's device")
+            res.iter_hist = iter_hist
+        return res
+
+    @staticmethod
+    def _es_check_exports(**exports):
+        bad = [k for k, v in exports.items() if v]
+        if bad:
+            raise ValueError("early_stop serves counters, flags, n_iter and iter_hist only, not " +
+                             ", ".join(bad))
+
+    def decode(self, llr, T: Optional[int] = None, app: Optional[bool] = None, hard: bool = False,
                synd: bool = False, counters=None, flags: bool = False, kernel: Optional[str] = None,
-               stream=None, target_bits: Optional[int] = None, iter_wrong: bool = False) -> DecodeResult:
+               stream=None, target_bits: Optional[int] = None, iter_wrong: bool = False,
+               early_stop: bool = False, n_iter: bool = False, iter_hist=None,
+               on_off_grid: str = "raise") -> DecodeResult:
         """Decode a batch.  ``counters`` may be a caller-owned int64[4] device tensor that is
         accumulated into (``+=``); pass ``True`` to get a fresh one.  ``target_bits``
         overrides the output / FER bit range (default Nt*z).  ``iter_wrong``: the per-iteration
-        frame-error words (every kernel, the counters-only ones included)."""
+        frame-error words (every kernel, the counters-only ones included).  ``app`` defaults to
+        True, and to False with ``early_stop``.
+
+        ``early_stop`` (opt-in, no counterpart in the reference): each frame stops at
+        the first iteration whose hard decisions have a zero syndrome and its outputs are frozen
+        there.  ``counters[0..2]`` and ``flags`` then describe the frames at their own stop
+        iteration (``counters[3]`` is left untouched), ``n_iter=True`` returns the iterations run
+        per frame (uint8 [B]) and ``iter_hist`` (``True`` or a caller-owned int64[T] tensor that is
+        accumulated into) their histogram.  ``app`` / ``hard`` / ``synd`` / ``iter_wrong`` are not
+        served and raise ``ValueError``.  The LLRs must lie on the quantizer grid: a pack of 32
+        frames holding an off-grid value is not decoded (``n_iter`` 0, ``flags`` 0x80, not
+        counted); ``on_off_grid="raise"`` synchronises and raises ``ValueError`` when there is one,
+        ``"mark"`` returns the result as it is."""
         torch = self._torch
         T = self.T if T is None else int(T)
         nt = self.target_bits if target_bits is None else int(target_bits)
         if T > self.T:
             raise ValueError(f"T={T} exceeds the {self.T} iterations the weights cover")
+        if early_stop:
+            self._es_check_exports(app=app, hard=hard, synd=synd, iter_wrong=iter_wrong)
+            if on_off_grid not in ("raise", "mark"):
+                raise ValueError("on_off_grid must be 'raise' or 'mark'")
+            llr = self._as_llr(llr)
+            B = int(llr.shape[0])
+            res = DecodeResult()
+            if B == 0:
+                return self._es_outputs(res, 0, T, counters, flags, n_iter, iter_hist)
+            ctx = self._ensure_ctx(B, T)
+            want_n = n_iter or on_off_grid == "raise"
+            self._es_outputs(res, B, T, counters, flags, want_n, iter_hist)
+            if stream is None:
+                stream = torch.cuda.current_stream(self.device)
+            ptr = lambda t: 0 if t is None else t.data_ptr()   # noqa: E731
+            self._ext.decode_es(ctx, llr.data_ptr(), B, T, self.decoding_type, self.q_bit, nt, self.clip,
+                                KERNELS[kernel or self.kernel], ptr(res.counters), ptr(res.flags),
+                                ptr(res.n_iter), ptr(res.iter_hist), stream.cuda_stream)
+            if on_off_grid == "raise":
+                stream.synchronize()
+                nbad = int((res.n_iter == 0).sum().item())
+                if nbad:
+                    raise ValueError(f"early_stop: {nbad} frames are in packs with LLRs off the quantizer "
+                                     "grid and were not decoded (on_off_grid='mark' returns them marked)")
+                if not n_iter:
+                    res.n_iter = None
+            return res
+        if n_iter or (iter_hist is not None and iter_hist is not False):
+            raise ValueError("n_iter and iter_hist are outputs of early_stop=True")
+        app = True if app is None else app
         llr = self._as_llr(llr)
         B = int(llr.shape[0])
         if B == 0:
@@ -225,14 +317,38 @@ class NMSDecoder:
 
     def decode_awgn(self, B: int, sigma: float, seed: int, offset: int = 0, punct=None, short=None,
                     T: Optional[int] = None, app: bool = False, counters=None, flags=None,
-                    kernel: Optional[str] = None, stream=None, iter_wrong: bool = False) -> DecodeResult:
+                    kernel: Optional[str] = None, stream=None, iter_wrong: bool = False,
+                    early_stop: bool = False, n_iter: bool = False, iter_hist=None) -> DecodeResult:
         """Decode B codewords whose LLRs come from the on-GPU AWGN channel, generated inside
         the decoder (``ldpc_decode_awgn``): identical to ``decode(awgn(...))`` without the
-        LLRs ever being written to HBM.  ``counters`` / ``flags`` as in ``decode``."""
+        LLRs ever being written to HBM.  ``counters`` / ``flags`` as in ``decode``;
+        ``early_stop`` / ``n_iter`` / ``iter_hist`` as in ``decode`` (the generated channel is
+        always on the grid)."""
         torch = self._torch
         T = self.T if T is None else int(T)
         punct = getattr(self, "punct", (0, 0)) if punct is None else punct
         short = getattr(self, "short", (0, 0)) if short is None else short
+        if early_stop:
+            self._es_check_exports(app=app, iter_wrong=iter_wrong)
+            if T > self.T:
+                raise ValueError(f"T={T} exceeds the {self.T} iterations the weights cover")
+            B = int(B)
+            res = DecodeResult()
+            if B == 0:
+                return self._es_outputs(res, 0, T, counters, flags, n_iter, iter_hist)
+            ctx = self._ensure_ctx(B, T)
+            self._es_outputs(res, B, T, counters, flags, n_iter, iter_hist)
+            if stream is None:
+                stream = torch.cuda.current_stream(self.device)
+            ptr = lambda t: 0 if t is None else t.data_ptr()   # noqa: E731
+            self._ext.decode_awgn_es(ctx, B, T, self.decoding_type, self.q_bit, self.target_bits,
+                                     self.clip, KERNELS[kernel or self.kernel], float(sigma), int(seed),
+                                     int(offset), int(punct[0]), int(punct[1]), int(short[0]),
+                                     int(short[1]), ptr(res.counters), ptr(res.flags), ptr(res.n_iter),
+                                     ptr(res.iter_hist), stream.cuda_stream)
+            return res
+        if n_iter or (iter_hist is not None and iter_hist is not False):
+            raise ValueError("n_iter and iter_hist are outputs of early_stop=True")
         if int(B) == 0:
             return self._empty_result(T, self.target_bits, False, False, counters, flags, app, iter_wrong)
         ctx = self._ensure_ctx(int(B), T)

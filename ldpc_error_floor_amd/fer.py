@@ -113,11 +113,13 @@ class SweepCheckpoint:
         return st
 
     def save(self, key, si, pos, counters, uncor_bytes=None, done=False, uncor_marks=None,
-             uncor_base=None):
+             uncor_base=None, iter_hist=None):
         st = {"version": CKPT_VERSION, "key": key, "si": int(si), "pos": int(pos),
               "counters": [[int(v) for v in row] for row in counters],
               "uncor_bytes": uncor_bytes, "uncor_marks": uncor_marks, "uncor_base": uncor_base,
               "done": bool(done), "time": time.time()}
+        if iter_hist is not None:       # early-stop sweeps: this rank's [nSNR, T] histogram
+            st["iter_hist"] = [[int(v) for v in row] for row in iter_hist]
         tmp = self.path + ".tmp"
         with open(tmp, "w") as f:
             json.dump(st, f)
@@ -152,7 +154,8 @@ def decoder_fingerprint(decoder, T=None):
 def fer_sweep(decoder, sigmas, n_codewords: int, batch: int, seed: int = 1076, T=None,
               punct=None, short=None, kernel=None, group=None, progress=None,
               uncor_path=None, checkpoint=None, checkpoint_every: int = 64,
-              resume: bool = False, point_seeds=None, overlap: bool = False):
+              resume: bool = False, point_seeds=None, overlap: bool = False,
+              early_stop: bool = False):
     """Decode ``n_codewords`` per SNR point (split across ranks) with GPU LLRs and device
     counters.  Returns a list of ``Counters`` (global totals on every rank).
 
@@ -188,7 +191,14 @@ def fer_sweep(decoder, sigmas, n_codewords: int, batch: int, seed: int = 1076, T
     measured on one MI355X when the bit-sliced kernels still read HBM LLRs
     (``tools/overlap_probe.py``, ``profiles/r3/overlap``), it gained nothing (C2 6.36 against
     6.29 ms per 2^20-codeword step, C4 / C5 equal, C3 1.6 % slower) — the channel kernel is
-    VALU-bound too and finds no idle issue slots beside the decode's waves."""
+    VALU-bound too and finds no idle issue slots beside the decode's waves.
+
+    ``early_stop``: decode with the syndrome stop rule (``NMSDecoder.decode(early_stop=True)``,
+    DESIGN.md 3.7; not the reference's full-T numbers): each ``Counters`` then describes the
+    frames at their own stop iteration (``loss2`` stays 0) and carries ``iter_hist``, the int64
+    [T] histogram of iterations run, kept beside the counters -- all-reduced with them and stored
+    in the checkpoint, whose key gains ``"early_stop": True`` (so a resume in the other mode is
+    refused).  Not with ``uncor_path``; a decoder without the mode is refused before any work."""
     import torch
     import torch.distributed as dist
     dist_on = dist.is_available() and dist.is_initialized()
@@ -204,6 +214,15 @@ def fer_sweep(decoder, sigmas, n_codewords: int, batch: int, seed: int = 1076, T
     punct = tuple(getattr(decoder, "punct", (0, 0)) if punct is None else punct)
     short = tuple(getattr(decoder, "short", (0, 0)) if short is None else short)
     counters = torch.zeros((sigmas.size, 4), dtype=torch.int64, device=dev)
+    hist = None
+    if early_stop:
+        if uncor_path is not None:
+            raise ValueError("early_stop does not collect uncorrected words (uncor_path)")
+        sup = getattr(decoder, "supports_early_stop", None)
+        if sup is None or not sup(T):
+            raise ValueError("this decoder does not serve early_stop (NMSDecoder.supports_early_stop)")
+        hist = torch.zeros((sigmas.size, int(decoder.T if T is None else T)), dtype=torch.int64, device=dev)
+    es_kw = {"early_stop": True} if early_stop else {}
     begin, end = shard_range(int(n_codewords), rank, world)
     # the channel generated inside the decoder (ldpc_decode_awgn) unless the decoder cannot;
     # collecting uncorrected words then regenerates only the failing frames' rows
@@ -232,6 +251,8 @@ def fer_sweep(decoder, sigmas, n_codewords: int, batch: int, seed: int = 1076, T
                "T": None if T is None else int(T), "punct": list(punct), "short": list(short),
                "rank": rank, "world": world, "uncor": upath is not None,
                "decoder": decoder_fingerprint(decoder, T), "channel": CHANNEL_STREAM}
+        if early_stop:                  # (only then: the keys of sweeps without the mode stay)
+            key["early_stop"] = True
         err = ""
         try:
             st = ck.load() if resume else None
@@ -251,6 +272,8 @@ def fer_sweep(decoder, sigmas, n_codewords: int, batch: int, seed: int = 1076, T
         if st is not None:
             si0, pos0 = st["si"], st["pos"]
             counters.copy_(torch.tensor(st["counters"], dtype=torch.int64))
+            if hist is not None:
+                hist.copy_(torch.tensor(st["iter_hist"], dtype=torch.int64))
             if upath is not None and st.get("uncor_bytes") is not None and os.path.exists(upath):
                 with open(upath, "r+b") as f:
                     f.truncate(int(st["uncor_bytes"]))
@@ -261,7 +284,8 @@ def fer_sweep(decoder, sigmas, n_codewords: int, batch: int, seed: int = 1076, T
 
     def save(si, pos, done=False):
         ub = fsize(upath) if upath else None
-        ck.save(key, si, pos, counters.cpu().tolist(), ub, done, marks if upath else None, base)
+        ck.save(key, si, pos, counters.cpu().tolist(), ub, done, marks if upath else None, base,
+                None if hist is None else hist.cpu().tolist())
 
     if ck is not None and st is None:
         # a fresh start records the uncorrected-word file's current length at once: a resume
@@ -269,7 +293,7 @@ def fer_sweep(decoder, sigmas, n_codewords: int, batch: int, seed: int = 1076, T
         # and rows earlier sweeps appended to a shared file stay (Print_Functions.py:122 appends)
         save(si0, pos0)
 
-    if fused_channel and upath is None and overlap and _pipelines(decoder, T, kernel):
+    if fused_channel and upath is None and overlap and not early_stop and _pipelines(decoder, T, kernel):
         # the channel of batch j + 1 on a second stream while batch j decodes (the decoder reads
         # its LLRs from HBM, so ldpc_decode_awgn would run the two kernels back to back)
         jobs = [(si, pos, min(batch, end - pos)) for si in range(si0, sigmas.size)
@@ -319,7 +343,8 @@ def fer_sweep(decoder, sigmas, n_codewords: int, batch: int, seed: int = 1076, T
                 # LLRs generated inside the decoder (ldpc_decode_awgn): no HBM round trip
                 fb = None if flag_bufs is None else flag_bufs[nb % 2][:b]
                 decoder.decode_awgn(b, float(sigma), point_seeds[si], offset=pos, punct=punct,
-                                    short=short, T=T, counters=counters[si], kernel=kernel, flags=fb)
+                                    short=short, T=T, counters=counters[si], kernel=kernel, flags=fb,
+                                    **(dict(es_kw, iter_hist=hist[si]) if early_stop else {}))
                 if fb is not None:
                     ev = torch.cuda.Event()
                     ev.record(torch.cuda.current_stream(dev))
@@ -329,7 +354,8 @@ def fer_sweep(decoder, sigmas, n_codewords: int, batch: int, seed: int = 1076, T
                 decoder.awgn(b, float(sigma), point_seeds[si], offset=pos, punct=punct,
                              short=short, out=llr[:b])
                 decoder.decode(llr[:b], T=T, app=False, counters=counters[si], kernel=kernel,
-                               flags=None if flags is None else flags[:b])
+                               flags=None if flags is None else flags[:b],
+                               **(dict(es_kw, iter_hist=hist[si]) if early_stop else {}))
                 if flags is not None:
                     rows = decoder.collect_uncorrected(flags[:b], llr[:b])
                     if rows.shape[0]:
@@ -349,11 +375,18 @@ def fer_sweep(decoder, sigmas, n_codewords: int, batch: int, seed: int = 1076, T
     if dist_on:
         # (a world of one included: the same collective the multi-GPU job runs)
         dist.all_reduce(counters, op=dist.ReduceOp.SUM, group=group)
+        if hist is not None:
+            dist.all_reduce(hist, op=dist.ReduceOp.SUM, group=group)
     if upath is not None and world > 1:
         _merge_uncor_files(uncor_path, marks, base, rank, world, group, counters.device)
     host = counters.cpu().numpy()
-    return [Counters.from_array(host[i], int(n_codewords), decoder.n_vars)
-            for i in range(sigmas.size)]
+    out = [Counters.from_array(host[i], int(n_codewords), decoder.n_vars)
+           for i in range(sigmas.size)]
+    if hist is not None:
+        hh = hist.cpu().numpy()
+        for i, c in enumerate(out):
+            c.iter_hist = hh[i].astype(np.int64).copy()
+    return out
 
 
 def _merge_uncor_files(uncor_path, marks, base, rank, world, group, device):

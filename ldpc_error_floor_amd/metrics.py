@@ -13,6 +13,7 @@ per frame 1/2 (1 - sign(min_k(-y_k))) in {0, 1/2, 1}.
 from __future__ import annotations
 
 from dataclasses import dataclass
+from typing import Optional
 
 import numpy as np
 
@@ -74,6 +75,9 @@ class Counters:
     loss2: int = 0
     frames: int = 0
     bits_per_frame: int = 0
+    # early-stop sweeps (fer_sweep(early_stop=True)): int64 [T], frames that ran t + 1 iterations;
+    # the counters then describe each frame at its own stop iteration and loss2 stays 0
+    iter_hist: Optional[np.ndarray] = None
 
     @classmethod
     def from_array(cls, arr, frames: int, bits_per_frame: int) -> "Counters":
@@ -95,3 +99,12 @@ class Counters:
     @property
     def loss(self) -> float:
         return 0.5 * self.loss2 / max(1, self.frames)
+
+    @property
+    def mean_iterations(self) -> Optional[float]:
+        """Mean iterations run per decoded frame (early-stop sweeps), or None without a histogram."""
+        if self.iter_hist is None:
+            return None
+        h = np.asarray(self.iter_hist, np.float64)
+        n = h.sum()
+        return float((h * np.arange(1, h.size + 1)).sum() / n) if n > 0 else 0.0

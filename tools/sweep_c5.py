@@ -52,7 +52,13 @@ def parse(argv=None):
                          "(the Uncor.txt format main_Post.py reads; one merged file at any --gpus)")
     ap.add_argument("--deep-snrs", default="",
                     help="skip the scan: decode --deep codewords at each of these SNRs only")
+    ap.add_argument("--early-stop", action="store_true",
+                    help="decode with the syndrome stop rule (fer_sweep(early_stop=True): each frame's "
+                         "outputs at its first zero-syndrome iteration, not the full-T numbers); "
+                         "records the mean iterations and their histogram per point; not with --uncor")
     a = ap.parse_args(argv)
+    if a.early_stop and a.uncor:
+        ap.error("--early-stop does not collect uncorrected words (--uncor)")
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
     return a
@@ -134,7 +140,8 @@ def main(argv=None, make_decoder=None):
         res = fer_sweep(dec, [sig[i] for i in idx], n, a.batch, seed=1076, progress=progress,
                         checkpoint=os.path.join(a.out, f"ckpt_{stage}.json"), checkpoint_every=16,
                         resume=True, point_seeds=[point_seed(snrs[i], stage) for i in idx],
-                        uncor_path=os.path.join(a.out, f"Uncor_{stage}.txt") if a.uncor else None)
+                        uncor_path=os.path.join(a.out, f"Uncor_{stage}.txt") if a.uncor else None,
+                        **({"early_stop": True} if a.early_stop else {}))
         if dev.type == "cuda":
             torch.cuda.synchronize(dev)
         dt = stage_time(time.time() - t0)
@@ -146,6 +153,9 @@ def main(argv=None, make_decoder=None):
                          "frame_err_any_iter": fa, "fer": fa / n,
                          "bit_err_last": int(c.bit_err_last),
                          "ber_last": int(c.bit_err_last) / (n * dec.n_vars)})
+            if a.early_stop:            # (the counters above: each frame at its stop iteration)
+                rows[-1]["mean_iterations"] = c.mean_iterations
+                rows[-1]["iter_hist"] = [int(x) for x in c.iter_hist]
             if rank == 0:
                 print(f"{stage} {snrs[i]:.2f} dB: FER_last {fe}/{n} = {fe / n:.3e}", flush=True)
         return rows, dt
@@ -167,7 +177,7 @@ def main(argv=None, make_decoder=None):
                "kernel": kernel, "n_gpus": world,
                "process_group": ({"backend": dist.get_backend(), "world": dist.get_world_size()}
                                  if dist.is_initialized() else None),
-               "batch_per_rank": a.batch, "scan": scan, "deep": deep,
+               "batch_per_rank": a.batch, "early_stop": bool(a.early_stop), "scan": scan, "deep": deep,
                "seconds": {"scan": round(t_scan, 1), "deep": round(t_deep, 1)},
                "codewords_total": n_total,
                "codewords_per_s": round(n_total / max(t_scan + t_deep, 1e-9), 1),
