@@ -191,9 +191,11 @@ int ldpc_awgn_in_kernel(const ldpc_ctx* ctx, const ldpc_decode_params* params, i
    counters nor the histogram.
    Served: QMS with q_bit 5, -5, 4 or 3, no per-edge check weights, kernel AUTO or FUSED,
    T <= T_max, a graph one of the bit-sliced kernel's early-stop instances fits (one 32-codeword
-   pack per workgroup: wman- and 802.11n-sized graphs).  Anything else returns
+   pack per workgroup: wman- and 802.11n-sized graphs), or, for a graph that only the compressed
+   bit-sliced kernel serves (5G BG1 n2112), that kernel's early-stop build, which exists for
+   channel weights that are all 1 (no UCN weights).  Anything else returns
    LDPC_ERR_UNSUPPORTED with nothing launched and no partial result.  ldpc_ctx_last_kernel
-   reports "bsl[...,es]" (and "+gen" when the channel was generated in the kernel).
+   reports "bsl[...,es]" or "bsc[...,es]" (and "+gen" when the channel was generated in the kernel).
    size: sizeof(ldpc_es_outputs) of the caller's header; any other value -> LDPC_ERR_ARG. */
 typedef struct ldpc_es_outputs {
     int32_t size;

@@ -24,7 +24,11 @@ extern "C" {
  * plan passes the test that lets that build run; the check then reports "channel tables".
  * flags bit 2 (LDPC_BOUNDS_ES): also check the plans of the early-stop instances (ldpc_decode_es),
  * with their hard-decision / syndrome reads on and their syndrome words in LDS; without it the
- * plans checked, and the count returned, are those of the decodes without the mode.  Only
+ * plans checked, and the count returned, are those of the decodes without the mode.  flags bit 3
+ * (LDPC_BOUNDS_ES_BSC = 8): also check the compressed kernel's early-stop plan where a decode in
+ * the mode would take it (no bsl plan serves the graph, uniform beta = 1: 5G BG1) -- its syndrome
+ * words inside the RED region and before the alpha table, the LDS size, and the chunk, position
+ * and channel-table checks of the bsc plan; one more plan in the count.  Only
  * the checks read the flags, no kernel or launch path does.  Returns the number of plans
  * checked (>= 0) or a negative status; *violations = out-of-bounds reads found, msg = the
  * first one ("" if none). */

@@ -891,17 +891,27 @@ int bs_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float*
 }
 
 // ---- early stop ---------------------------------------------------------------
+// The compressed kernel's early-stop builds (bsc_*_es) serve the request exactly where bs_decode
+// falls through to bsc_decode: when no bsl plan at all serves the graph.  (A graph that a
+// multi-chunk bsl instance serves, 5G BG2, would fit bsc too, but its decodes never run there: it
+// has no early-stop build.)
+static bool es_falls_to_bsc(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T) {
+    return !bs_plan(g, mode, ucn, per_edge_w, clip, T).ok;
+}
 bool bs_es_supported(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T) {
-    return bs_plan(g, mode, ucn, per_edge_w, clip, T, true).ok;
+    if (bs_plan(g, mode, ucn, per_edge_w, clip, T, true).ok) return true;
+    return es_falls_to_bsc(g, mode, ucn, per_edge_w, clip, T) && bsc_es_supported(g, mode, ucn, per_edge_w, clip, T);
 }
 bool bs_es_q8_ok(const DevGraph& g, int mode, bool ucn, float clip, int T, bool has_short) {
     const BsPlan p = bs_plan(g, mode, ucn, false, clip, T, true);
-    return p.ok && (!has_short || p.cu > 0.f) && q8_tab_fits(p);
+    if (!p.ok) return es_falls_to_bsc(g, mode, ucn, false, clip, T) && bsc_es_q8_ok(g, mode, ucn, clip, T, has_short);
+    return (!has_short || p.cu > 0.f) && q8_tab_fits(p);
 }
 const char* bs_es_kernel_name(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T) {
     static thread_local char buf[64];
     const BsPlan p = bs_plan(g, mode, ucn, per_edge_w, clip, T, true);
-    if (!p.ok) return "";
+    if (!p.ok)
+        return es_falls_to_bsc(g, mode, ucn, per_edge_w, clip, T) ? bsc_es_kernel_name(g, mode, ucn, per_edge_w, clip, T) : "";
     const BsInst& k = kBsInst[p.inst];
     snprintf(buf, sizeof(buf), "bsl[p32,w%d,d%d,v%d,l%d%s,es]", p.nw, k.D, k.DV, k.LPC, p.ucn ? ",ucn" : "");
     return buf;
@@ -914,7 +924,10 @@ int bs_decode_es(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const flo
                  int ntiles_max, int64_t* counters, uint8_t* flags, uint8_t* n_iter, int64_t* iter_hist,
                  hipStream_t s) {
     const BsPlan p = bs_plan(g, mode, ucn, false, b.clip, b.T, true);
-    if (!p.ok) return LDPC_ERR_UNSUPPORTED;
+    // (no bsl plan at all: the compressed kernel's early-stop builds, as bs_decode's fall-through)
+    const bool to_bsc = !p.ok && es_falls_to_bsc(g, mode, ucn, false, b.clip, b.T) &&
+                        bsc_es_supported(g, mode, ucn, false, b.clip, b.T);
+    if (!p.ok && !to_bsc) return LDPC_ERR_UNSUPPORTED;
     if (b.q8 && !bs_es_q8_ok(g, mode, ucn, b.clip, b.T, reinterpret_cast<const AwgnParams*>(b.gen8)->ss > 0))
         return LDPC_ERR_UNSUPPORTED;
     const int64_t npk = (b.B + 31) / 32;
@@ -929,6 +942,7 @@ int bs_decode_es(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const flo
         }
         ws.bs_bad_n = n;
     }
+    if (to_bsc) return bsc_decode_es(g, b, ws, llr, mode, ucn, counters, flags, ws.bs_bad, n_iter, iter_hist, s);
     const EsOut es{n_iter, iter_hist};
     return bs_run(g, b, ws, p, llr, mode, ucn, counters, flags, ws.bs_bad, nullptr, &es, s);
 }
@@ -1169,6 +1183,18 @@ extern "C" int ldpc_debug_bs_bounds(const int32_t* proto, int32_t M, int32_t N, 
         ++checked;
         if (r.violations && first.empty()) first = std::string(b1 ? "bsc beta=1: " : "bsc: ") + r.first;
         *violations += r.violations;
+    }
+    // (the compressed kernel's early-stop plan with LDPC_BOUNDS_ES_BSC only: on top of its
+    // beta = 1 build, so for a uniform beta alone, and where the early-stop decode falls through to
+    // it: no bsl plan serves the graph; one more checked plan where it exists)
+    g.w_beta_one = 1;
+    if ((flags & LDPC_BOUNDS_ES_BSC) && beta_uniform && !bs_plan(g, mode, false, false, clip, T).ok) {
+        BoundsReport r;
+        if (bsc_debug_bounds(g, mode, clip, T, flags, r.violations, r.first, true) > 0) {
+            ++checked;
+            if (r.violations && first.empty()) first = std::string("bsc early stop: ") + r.first;
+            *violations += r.violations;
+        }
     }
     if (msg && msg_len > 0) {
         std::strncpy(msg, first.c_str(), (size_t)msg_len - 1);

@@ -75,6 +75,15 @@ struct BscArgs {
     BsGen gen;                   // Q8 builds: the in-prologue channel (bsl's; tables at SGN)
 };
 
+// The early-stop builds' arguments: BscArgs and what the mode adds, so the other
+// builds' kernel arguments stay as they are.
+struct BscArgsEs : BscArgs {
+    uint8_t* n_iter;             // [B] iterations run per codeword (0: pack off the grid), or null
+    int64_t* iter_hist;          // [T] += codewords with n_iter = t + 1, or null
+    uint32_t off_u;              // LDS: the T syndrome words, after the FLORW words of RED: word t
+                                 // = OR over the checks of the syndrome of iteration t's hard decisions
+};
+
 typedef unsigned int v2u __attribute__((ext_vector_type(2)));
 
 // Check records in blocks of 16: the q1 words of records 16 b .. 16 b + 15 (256 B), then their q2
@@ -95,9 +104,15 @@ __device__ __forceinline__ void lds_dput(uint32_t addr, uint32_t x, uint32_t y) 
 // B1: every beta is 1 and one column table (a.beta_id, bcols 1: C5's flat weights), so the
 // channel term is Q(ch) itself and neither the beta table's operands nor the shortened-bit
 // planes are live (C5's instance: 124 VGPRs, no spills, against 128 and 10 spilled)
-template <int D, int DVH, int DVL, int LPC, int VPL, int CPL, int WPE, bool XP, int LB, bool MIX, bool B1, bool Q8>
+// ES: the early-stop build, on top of B1 only.  There the Tv that the variable phase
+// stores is clamp6(Q(ch) + S), whose sign is the sign of APP_t bit for bit (the same planes into
+// the same adder), so iteration t's hard decisions are ~TV[v] plane 5 and need no table of their
+// own: check phase t + 1 XORs them over each check's real edges into syndrome word U[t].
+template <int D, int DVH, int DVL, int LPC, int VPL, int CPL, int WPE, bool XP, int LB, bool MIX, bool B1, bool Q8,
+          bool ES = false>
 __global__ void __launch_bounds__(LB) __attribute__((amdgpu_waves_per_eu(WPE)))
-k_bsc(BscArgs a) {
+k_bsc(std::conditional_t<ES, BscArgsEs, BscArgs> a) {
+    static_assert(!ES || (B1 && !XP), "early stop: the beta = 1 build, no export");
     constexpr int SB = (DVH * QMAX + QMAX <= 127) ? 8 : 9;
     constexpr int EPL = (D + LPC - 1) / LPC;
     constexpr int VNW = DVH + 1;
@@ -181,6 +196,14 @@ k_bsc(BscArgs a) {
     if (off) atomicOr(&RED[7], 1u);
     __syncthreads();
     if (RED[7]) {
+        if constexpr (ES) {
+            // early stop: no fixup; the pack's frames are marked undecoded and enter neither the
+            // counters nor the histogram
+            if (tid < nvalid) {
+                if (a.flags) a.flags[b0 + tid] = 0x80;
+                if (a.n_iter) a.n_iter[b0 + tid] = 0;
+            }
+        }
         if (tid == 0) a.bad[blockIdx.x] = 1u;
         return;
     }
@@ -190,6 +213,13 @@ k_bsc(BscArgs a) {
         reinterpret_cast<uint32_t*>(smem + a.off_rec + rec_off((uint32_t)a.n_checks) + (tid >> 2) * REC_Q2)[tid & 3] = 0u;
     if (tid < 8) RED[tid] = (tid == 1) ? 0xFFFFFFFFu : 0u;
     if (tid < FLORW) RED[flor + tid] = 0u;
+    // early stop: the done word (wave-uniform, every wave its own copy: a codeword's bit is set once
+    // an iteration's hard decisions had a zero syndrome; the bits past the pack's codewords start
+    // set, so a ragged pack's padding never holds the pack back) and the T syndrome words, zeroed
+    [[maybe_unused]] uint32_t es_done = ~valid;
+    if constexpr (ES) {
+        for (int w = tid; w < a.T; w += NT) (RED + ((a.off_u - a.off_red) >> 2))[w] = 0u;
+    }
     for (int w = tid; w < AL; w += NT) ALUT[w] = a.alut[w];
     for (int w = tid; w < BL; w += NT) BLUT[w] = a.blut[w];
     __syncthreads();
@@ -282,7 +312,9 @@ k_bsc(BscArgs a) {
                         wr |= hd;
                         if (last) {
                             apos |= hd & nz;
-                            nb += (uint32_t)__popc(hd);
+                            // (early stop: the codewords not done before count from iteration T - 1)
+                            if constexpr (ES) nb += (uint32_t)__popc(hd & ~es_done);
+                            else nb += (uint32_t)__popc(hd);
                         }
                     }
                 }
@@ -433,6 +465,9 @@ k_bsc(BscArgs a) {
                 q2o = lds_q(grec[c] + REC_Q2);
             }
             uint32_t Xs[EPL][4], ns[EPL];
+            // early stop: the lane's share of its check's syndrome of iteration t - 1's hard
+            // decisions (~Tv plane 5), over its real edge positions only
+            [[maybe_unused]] uint32_t syn = 0u;
 #pragma unroll
             for (int m = 0; m < EPL; ++m) {
                 if (m >= gmc) {                      // padding for the whole chunk
@@ -462,10 +497,25 @@ k_bsc(BscArgs a) {
                 }
                 abs_sat(Xs[m], x);
                 ns[m] = x[6];
+                if constexpr (ES) {
+                    if (t > 0 && real(m)) syn ^= ~Tv[5];
+                }
                 if (!real(m)) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) Xs[m][i] = ~0u;
                     ns[m] = ~0u;
+                }
+            }
+            if constexpr (ES) {
+                // merged over the check's lanes as par; the lanes that hold a check OR theirs into
+                // syndrome word t - 1 (one LDS atomic per wave and chunk)
+                if (t > 0) {
+                    syn ^= qperm<QP_X1>(syn);
+                    if (L == 4) syn ^= qperm<QP_X2>(syn);
+                    const uint32_t wu = wave_or(has_check ? syn : 0u);
+                    if (wu && lane == 0)
+                        __hip_atomic_fetch_or((RED + ((a.off_u - a.off_red) >> 2)) + (t - 1), wu,
+                                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
             }
             // two minima by the bit-serial search of bsl (min2_bits) over the chunk's real positions
@@ -532,12 +582,94 @@ k_bsc(BscArgs a) {
             else if constexpr (MIX) chunk(std::integral_constant<int, LPC / 2>{});
         }
         __syncthreads();
+        if constexpr (ES) {
+            // ======== early stop ================================================================
+            // syndrome word t - 1 is complete (the barrier): the codewords newly done at iteration
+            // t - 1 are those with no unsatisfied check that were not done before.  Their bit
+            // errors are counted from TV, which still holds iteration t - 1's value; once every
+            // codeword is done the workgroup leaves the loop (every wave reads the same word: a
+            // workgroup-uniform branch; the barrier retired the async table copies).
+            if (t > 0) {
+                const uint32_t un = (uint32_t)__builtin_amdgcn_readfirstlane(
+                    (int)(RED + ((a.off_u - a.off_red) >> 2))[t - 1]);
+                const uint32_t nn = ~un & ~es_done;
+                es_done |= nn;
+                if (nn) {
+                    uint32_t nb = 0u;
+#pragma unroll
+                    for (int u = 0; u < VPL; ++u) {
+                        const int v = vv[u] < 0 ? -1 : (vv[u] & 0xFFFF);
+                        if (v >= 0 && v < a.target_bits)
+                            nb += (uint32_t)__popc(~lds_w(a.off_tv + 24u * ((uint32_t)vv[u] >> 16) + 20u) & nn);
+                    }
+                    nb = wave_add(nb);
+                    if (nb && lane == 0) atomicAdd(&RED[3], nb);
+                }
+                if (es_done == 0xFFFFFFFFu) break;
+            }
+        }
         // ======== variable nodes ================================================================
         const uint32_t bslice = a.off_blut + (uint32_t)(nx * BL * 4);
         if (t == a.T - 1) vn_phase(false, true, bslice, t + 1);
         else vn_phase(false, false, bslice, t + 1);
         __syncthreads();
     }
+    if constexpr (ES) {
+        // early stop: each codeword's outputs at its own stop iteration -- the first t whose
+        // syndrome word has its bit clear, else T - 1 -- from the syndrome words and the
+        // per-iteration frame-error words (RED[16 + t]; iteration T - 1's is RED[0]); one lane of
+        // wave 0 per codeword, as the bsl build.  (The words past the iteration the pack left the
+        // loop at are not used: every codeword has stopped by then.)
+        __syncthreads();                 // the bit counts of the waves that left the loop
+        if (wave == 0) {
+            const uint32_t* U = (RED + ((a.off_u - a.off_red) >> 2));
+            const int r = tid & 31;
+            const bool on = tid < nvalid;
+            int stop = a.T - 1;
+            uint32_t all = 1u, wl = 0u;
+            bool open = true;
+            for (int t = 0; t < a.T; ++t) {
+                const bool lastt = t == a.T - 1;
+                const uint32_t w = lastt ? RED[0] : RED[16 + t];
+                const uint32_t u = lastt ? 0u : U[t];
+                if (open) {
+                    wl = (w >> r) & 1u;
+                    all &= wl;
+                    if (!((u >> r) & 1u)) {
+                        stop = t;
+                        open = false;
+                    }
+                }
+            }
+            const unsigned long long mw = __builtin_amdgcn_ballot_w64(on && wl != 0u);
+            const unsigned long long ma = __builtin_amdgcn_ballot_w64(on && all != 0u);
+            if (on) {
+                if (a.flags) a.flags[b0 + tid] = (uint8_t)(all | (wl << 1));
+                if (a.n_iter) a.n_iter[b0 + tid] = (uint8_t)(stop + 1);
+            }
+            if (tid == 0 && a.counters) {
+                unsigned long long* cc = reinterpret_cast<unsigned long long*>(a.counters);
+                const unsigned long long c0 = RED[3], c1 = __popcll(mw), c2 = __popcll(ma);
+                if (c0) atomicAdd(cc + 0, c0);
+                if (c1) atomicAdd(cc + 1, c1);
+                if (c2) atomicAdd(cc + 2, c2);
+            }
+            if (a.iter_hist) {                  // one atomic per distinct stop iteration of the pack
+                unsigned long long rem = __builtin_amdgcn_ballot_w64(on);
+                while (rem) {
+                    const int l = __builtin_ctzll(rem);
+                    const int ts = __builtin_amdgcn_readlane(stop, l);
+                    const unsigned long long m = __builtin_amdgcn_ballot_w64(on && stop == ts);
+                    if (tid == l)
+                        atomicAdd(reinterpret_cast<unsigned long long*>(a.iter_hist) + ts,
+                                  (unsigned long long)__popcll(m));
+                    rem &= ~m;
+                }
+            }
+        }
+    }
+    if constexpr (!ES) {
+    // (the body keeps the indentation it had before the early-stop builds)
     if (tid == 0) {
         const uint32_t wl = RED[0] & valid;
         const uint32_t all = RED[1] & RED[0] & valid;
@@ -562,6 +694,7 @@ k_bsc(BscArgs a) {
         if (a.iter_wrong)
             for (int t = tid; t < a.T; t += NT)
                 a.iter_wrong[(size_t)t * (size_t)((a.B + 31) >> 5) + blockIdx.x] = RED[16 + t] & valid;
+    }
     }
 }
 
@@ -597,6 +730,8 @@ struct BscPlan {
     float cu = -1.f;
     size_t nslot = 0;
     uint32_t off_a = 0, off_rec = 0, off_tv = 0, off_red = 0, off_alut = 0, off_blut = 0;
+    bool es = false;               // an early-stop plan:
+    uint32_t off_u = 0;            // its T syndrome words (in the RED region, after the FLORW words)
     size_t lds = 0;
     std::vector<int32_t> lay;
     std::vector<int> vorder, vslot;      // variables by degree; chunk of each (wave, u) place
@@ -610,12 +745,25 @@ struct BscPlan {
 static uint32_t q8_tab_lds(const BscPlan&) { return 0u; }
 static bool q8_tab_fits(const BscPlan& p) { return (size_t)p.off_a >= sizeof(uint32_t) * AWGN_TAB_W; }
 
-static BscPlan bsc_plan(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T) {
+// (LDPC_BSC_B1=0: the general channel path for a B1 decode too, an A/B switch)
+static bool bsc_b1_on() {
+    static const bool on = [] { const char* e = getenv("LDPC_BSC_B1"); return !(e && atoi(e) == 0); }();
+    return on;
+}
+// the early-stop builds exist for these instances (on top of their B1 build)
+static constexpr bool bsc_es_inst(int i) { return i == 3 || i == 4; }
+
+// es: the plan of an early-stop request.  Only a decode that takes the B1 build
+// (every beta 1, one column table) on the instance the planner picks for it has such a build; the
+// plan is that decode's with the T syndrome words added.  Every other request has no plan.
+static BscPlan bsc_plan(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T,
+                        bool es = false) {
     BscPlan p;
     const char* e = getenv("LDPC_BS");
     if (e && atoi(e) == 0) return p;
     if (!bs_mode(mode)) return p;
     if (ucn || per_edge_w || !g.host || !g.w_beta_nonneg) return p;
+    if (es && !(g.w_beta_one && g.w_beta_uniform && bsc_b1_on())) return p;
     const host::GraphTables& h = *g.host;
     int min_cdeg = 1 << 30;
     for (int i = 0; i < h.M; ++i) min_cdeg = std::min(min_cdeg, h.row_ptr[i + 1] - h.row_ptr[i]);
@@ -712,12 +860,20 @@ static BscPlan bsc_plan(const DevGraph& g, int mode, bool ucn, bool per_edge_w, 
         q.off_red = (uint32_t)o;
         o += 64 + (((size_t)4 * T + 15) & ~(size_t)15) + 4 * FLORW;      // + the frame-error words
                                                                        // (16 B aligned), the OR words
+        if (es) {                  // + the T syndrome words of the early-stop builds, rounded alike
+            q.es = true;
+            q.off_u = (uint32_t)o;
+            o += ((size_t)4 * T + 15) & ~(size_t)15;
+        }
         q.off_alut = (uint32_t)o;
         o += (size_t)2 * q.arows * LUT_W * 4;
         q.off_blut = (uint32_t)o;
         o += (size_t)2 * q.bcols * BLUT_W * 4;
         q.lds = (o + 15) & ~(size_t)15;
         if (q.lds > BS_LDS_MAX) continue;
+        // (early stop: the instance the full-T decode would take, or none -- a forced instance
+        // without the build is not replaced by another)
+        if (es && (!bsc_es_inst(i) || q.bcols != 1)) return p;
         q.ok = true;
         return q;
     }
@@ -847,9 +1003,7 @@ static int bsc_launch1(const BscArgs& a, int nblocks, int nw, size_t lds, hipStr
 }
 template <int I, bool XP>
 static int bsc_launch(const BscArgs& a, int nblocks, int nw, size_t lds, hipStream_t s, bool q8) {
-    // (LDPC_BSC_B1=0: the general channel path for a B1 decode too, an A/B switch)
-    static const bool b1_on = [] { const char* e = getenv("LDPC_BSC_B1"); return !(e && atoi(e) == 0); }();
-    const bool b1 = b1_on && a.beta_id && a.bcols == 1;
+    const bool b1 = bsc_b1_on() && a.beta_id && a.bcols == 1;
     if constexpr (XP) {
         // (the generated channel comes from ldpc_decode_awgn, which exports no hard bits)
         if (q8) return LDPC_ERR_UNSUPPORTED;
@@ -859,6 +1013,22 @@ static int bsc_launch(const BscArgs& a, int nblocks, int nw, size_t lds, hipStre
     }
     if (b1) return bsc_launch1<I, XP, true, false>(a, nblocks, nw, lds, s);
     return bsc_launch1<I, XP, false, false>(a, nblocks, nw, lds, s);
+}
+// the early-stop builds of instance I (float LLRs, or the in-prologue channel): the B1 build, one
+// workgroup per pack, no export build
+template <int I, bool Q8>
+static int bsc_launch_es(const BscArgsEs& a, int nblocks, int nw, size_t lds, hipStream_t s) {
+    constexpr BscInst k = kBscInst[I];
+    static_assert(bsc_es_inst(I) && k.MIX, "an early-stop instance");
+    auto* fn = &k_bsc<k.D, k.DVH, k.DVL, k.LPC, k.VPL, k.CPL, k.WPE, false, 64 * k.NW, k.MIX, true, Q8, true>;
+    static bool attr = false;
+    if (!attr) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)BS_LDS_MAX);
+        attr = true;
+    }
+    hipLaunchKernelGGL(fn, dim3(nblocks), dim3(64 * nw), lds, s, a);
+    return hipGetLastError() == hipSuccess ? LDPC_OK : LDPC_ERR_HIP;
 }
 
 }  // namespace bs
@@ -873,9 +1043,12 @@ using namespace bs;
 // wave_or / popc over its lanes, restated -- is in 1 .. EPL, the range the min2 switch covers
 // (its other cases are marked unreachable).  Returns 1 if a plan was checked, 0 if
 // none serves the graph; violations / first as BoundsReport.
+// es: the early-stop plan of the graph instead (LDPC_BOUNDS_ES_BSC): the same checks, and its T
+// syndrome words lie inside the RED region, after the FLORW words and before ALUT, with the
+// dynamic LDS size inside BS_LDS_MAX.
 int bsc_debug_bounds(const DevGraph& g, int mode, float clip, int T, int flags, int& violations,
-                     std::string& first) {
-    const BscPlan p = bsc_plan(g, mode, false, false, clip, T);
+                     std::string& first, bool es) {
+    const BscPlan p = bsc_plan(g, mode, false, false, clip, T, es);
     if (!p.ok) return 0;
     auto fail = [&](const char* what, long long idx, long long lo, long long hi) {
         if (violations++ == 0) {
@@ -887,6 +1060,15 @@ int bsc_debug_bounds(const DevGraph& g, int mode, float clip, int T, int flags, 
     const host::GraphTables& h = *g.host;
     const BscInst& k = kBscInst[p.inst];
     const int LPC = k.LPC, EPL = (k.D + LPC - 1) / LPC, z = h.z, nc = g.n_checks;
+    if (es) {
+        // RED: 16 words, the frame-error words (T rounded to 4), the FLORW words, then U[0 .. T)
+        const long long u0 = p.off_u, un = 4LL * T;
+        const long long red_used = (long long)p.off_red + 4LL * (16 + ((T + 3) & ~3) + FLORW);
+        if (!p.es || u0 < red_used || u0 + un > (long long)p.off_alut)
+            fail("syndrome words", u0 + un, red_used, p.off_alut);
+        if (u0 & 15) fail("syndrome words' alignment", u0 & 15, 0, 1);
+        if (p.lds > BS_LDS_MAX) fail("LDS size", (long long)p.lds, 0, (long long)BS_LDS_MAX + 1);
+    }
     if (q8_tab_fits(p)) {
         const long long tb = q8_tab_lds(p);
         const long long tn = (flags & LDPC_BOUNDS_BIG_TABLES) ? (long long)p.off_a + 4 : 4LL * AWGN_TAB_W;
@@ -937,10 +1119,30 @@ const char* bsc_kernel_name(const DevGraph& g, int mode, bool ucn, bool per_edge
     return buf;
 }
 
-int bsc_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode,
-               bool ucn, int64_t* counters, uint8_t* flags, uint32_t* bad, uint32_t* hdx, hipStream_t s) {
-    const BscPlan p = bsc_plan(g, mode, ucn, false, b.clip, b.T);
-    if (!p.ok) return LDPC_ERR_UNSUPPORTED;
+// ---- early stop ---------------------------------------------------------------
+bool bsc_es_supported(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T) {
+    return bsc_plan(g, mode, ucn, per_edge_w, clip, T, true).ok;
+}
+bool bsc_es_q8_ok(const DevGraph& g, int mode, bool ucn, float clip, int T, bool has_short) {
+    const BscPlan p = bsc_plan(g, mode, ucn, false, clip, T, true);
+    return p.ok && (!has_short || p.cu > 0.f) && q8_tab_fits(p);
+}
+const char* bsc_es_kernel_name(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T) {
+    static thread_local char buf[64];
+    const BscPlan p = bsc_plan(g, mode, ucn, per_edge_w, clip, T, true);
+    if (!p.ok) return "";
+    const BscInst& k = kBscInst[p.inst];
+    snprintf(buf, sizeof(buf), "bsc[p32,w%d,d%d,v%d/%d,l%d%s,x%d/%d,es]", p.nw, k.D, k.DVH, k.DVL, k.LPC,
+             k.MIX ? "/2" : "", k.VPL, k.CPL);
+    return buf;
+}
+
+// one launch of plan p; es: the early-stop outputs (an early-stop plan), else null
+struct BscEsOut { uint8_t* n_iter; int64_t* iter_hist; };
+static int bsc_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const BscPlan& p, const float* llr, int mode,
+                   int64_t* counters, uint8_t* flags, uint32_t* bad, uint32_t* hdx, const BscEsOut* es,
+                   hipStream_t s) {
+    // (the graph tables do not depend on the mode: both kinds of decode share them)
     int st = bsc_tables(g, p, ws, s);
     if (st != LDPC_OK) return st;
     const BscInst& k = kBscInst[p.inst];
@@ -950,7 +1152,14 @@ int bsc_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float
     if (st != LDPC_OK) return st;
     const uint32_t* gt = reinterpret_cast<const uint32_t*>(ws.bs_graph);
     const int VNW = k.DVH + 1;
-    BscArgs a{};
+    // (BscArgs, and the early-stop builds' additions: their launch reads them, every other launch
+    // takes the BscArgs base alone)
+    BscArgsEs a{};
+    if (es) {
+        a.n_iter = es->n_iter;
+        a.iter_hist = es->iter_hist;
+        a.off_u = p.off_u;
+    }
     const bool q8 = b.q8 != nullptr;
     a.llr = llr;
     if (b.q8) {                          // the in-prologue channel (ldpc_decode_awgn)
@@ -987,7 +1196,8 @@ int bsc_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float
     a.cn_chunk = a.row_lay + 2 * (size_t)g.M;
     a.cn_var = reinterpret_cast<const uint32_t*>(a.cn_chunk + (size_t)p.nw * k.CPL);
     a.cn_lane = reinterpret_cast<const int32_t*>(a.cn_var + (size_t)p.cn_lanes * ((((k.D + k.LPC - 1) / k.LPC) + 1) / 2));
-    bs_stagger(false, &a.stagger, &a.stagger_n);     // (LDPC_BS_STAGGER still applies; C5: no gain)
+    // (LDPC_BS_STAGGER still applies; C5: no gain.  Early stop: none, the packs end at different times)
+    if (!es) bs_stagger(false, &a.stagger, &a.stagger_n);
     a.alut = alut;
     a.blut = blut;
     a.arows = p.arows;
@@ -995,7 +1205,7 @@ int bsc_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float
     a.counters = counters;
     a.flags = flags;
     a.bad = bad;
-    a.iter_wrong = b.iter_wrong;
+    a.iter_wrong = es ? nullptr : b.iter_wrong;
     a.hdx = hdx;
     a.off_a = p.off_a;
     a.off_rec = p.off_rec;
@@ -1004,6 +1214,14 @@ int bsc_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float
     a.off_alut = p.off_alut;
     a.off_blut = p.off_blut;
     const int nblocks = (int)((b.B + PACK - 1) / PACK);
+    if (es) {
+        if (hdx || !p.es || !a.beta_id || a.bcols != 1) return LDPC_ERR_UNSUPPORTED;
+        switch (p.inst) {
+            case 3: return q8 ? bsc_launch_es<3, true>(a, nblocks, p.nw, p.lds, s) : bsc_launch_es<3, false>(a, nblocks, p.nw, p.lds, s);
+            case 4: return q8 ? bsc_launch_es<4, true>(a, nblocks, p.nw, p.lds, s) : bsc_launch_es<4, false>(a, nblocks, p.nw, p.lds, s);
+            default: return LDPC_ERR_UNSUPPORTED;
+        }
+    }
     switch (p.inst) {
         case 1: return hdx ? bsc_launch<1, true>(a, nblocks, p.nw, p.lds, s, q8) : bsc_launch<1, false>(a, nblocks, p.nw, p.lds, s, q8);
         case 2: return hdx ? bsc_launch<2, true>(a, nblocks, p.nw, p.lds, s, q8) : bsc_launch<2, false>(a, nblocks, p.nw, p.lds, s, q8);
@@ -1011,6 +1229,26 @@ int bsc_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float
         case 4: return hdx ? bsc_launch<4, true>(a, nblocks, p.nw, p.lds, s, q8) : bsc_launch<4, false>(a, nblocks, p.nw, p.lds, s, q8);
         default: return hdx ? bsc_launch<0, true>(a, nblocks, p.nw, p.lds, s, q8) : bsc_launch<0, false>(a, nblocks, p.nw, p.lds, s, q8);
     }
+}
+
+int bsc_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode,
+               bool ucn, int64_t* counters, uint8_t* flags, uint32_t* bad, uint32_t* hdx, hipStream_t s) {
+    const BscPlan p = bsc_plan(g, mode, ucn, false, b.clip, b.T);
+    if (!p.ok) return LDPC_ERR_UNSUPPORTED;
+    return bsc_run(g, b, ws, p, llr, mode, counters, flags, bad, hdx, nullptr, s);
+}
+
+// the early-stop decode (as bs_decode_es, which falls through to it): LDPC_ERR_UNSUPPORTED with
+// nothing launched when no early-stop build serves the request
+int bsc_decode_es(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode, bool ucn,
+                  int64_t* counters, uint8_t* flags, uint32_t* bad, uint8_t* n_iter, int64_t* iter_hist,
+                  hipStream_t s) {
+    const BscPlan p = bsc_plan(g, mode, ucn, false, b.clip, b.T, true);
+    if (!p.ok) return LDPC_ERR_UNSUPPORTED;
+    if (b.q8 && !bsc_es_q8_ok(g, mode, ucn, b.clip, b.T, reinterpret_cast<const AwgnParams*>(b.gen8)->ss > 0))
+        return LDPC_ERR_UNSUPPORTED;
+    const BscEsOut es{n_iter, iter_hist};
+    return bsc_run(g, b, ws, p, llr, mode, counters, flags, bad, nullptr, &es, s);
 }
 
 }  // namespace ldpc

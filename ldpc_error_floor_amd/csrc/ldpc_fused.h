@@ -72,12 +72,14 @@ bool bs_q8_ok(const DevGraph& g, int mode, bool ucn, float clip, int T, bool has
 bool bsc_q8_ok(const DevGraph& g, int mode, bool ucn, float clip, int T, bool has_short);
 // host-side bounds check of the bsc plan (test infrastructure, ldpc_debug_bs_bounds), and the
 // flags of that check (include/ldpc_nms_debug.h): no kernel or launch path reads them
-enum { LDPC_BOUNDS_PRE_GUARD = 1, LDPC_BOUNDS_BIG_TABLES = 2, LDPC_BOUNDS_ES = 4 };
+enum { LDPC_BOUNDS_PRE_GUARD = 1, LDPC_BOUNDS_BIG_TABLES = 2, LDPC_BOUNDS_ES = 4, LDPC_BOUNDS_ES_BSC = 8 };
+// (es: the graph's early-stop plan instead, LDPC_BOUNDS_ES_BSC)
 int bsc_debug_bounds(const DevGraph& g, int mode, float clip, int T, int flags, int& violations,
-                     std::string& first);
-// early stop (ldpc_decode_es): the bit-sliced kernel's ES instances serve the request;
+                     std::string& first, bool es = false);
+// early stop (ldpc_decode_es): the bit-sliced kernel's ES instances serve the request,
+// or, for a graph that no bsl plan serves, the compressed kernel's early-stop builds (bsc_*_es);
 // their decode (counters [0..2], frame flags, n_iter [B], iter_hist [T], each or null; b.q8 / gen8:
-// the in-prologue channel, when bs_es_q8_ok) and its kernel name ("bsl[...,es]")
+// the in-prologue channel, when bs_es_q8_ok) and its kernel name ("bsl[...,es]" / "bsc[...,es]")
 bool bs_es_supported(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T);
 bool bs_es_q8_ok(const DevGraph& g, int mode, bool ucn, float clip, int T, bool has_short);
 const char* bs_es_kernel_name(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T);
@@ -93,6 +95,14 @@ bool bsc_supported(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float
 const char* bsc_kernel_name(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T);
 int bsc_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode,
                bool ucn, int64_t* counters, uint8_t* flags, uint32_t* bad, uint32_t* hdx, hipStream_t s);
+// its early-stop builds: the beta = 1 build of the mixed-lane instances (bs_*_es fall through to
+// these where bs_decode falls through to bsc_decode); kernel name "bsc[...,es]"
+bool bsc_es_supported(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T);
+bool bsc_es_q8_ok(const DevGraph& g, int mode, bool ucn, float clip, int T, bool has_short);
+const char* bsc_es_kernel_name(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T);
+int bsc_decode_es(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode, bool ucn,
+                  int64_t* counters, uint8_t* flags, uint32_t* bad, uint8_t* n_iter, int64_t* iter_hist,
+                  hipStream_t s);
 void fused_free(FusedWorkspace& ws);
 
 // float-mode fused decoder (ldpc_ffl.hip): MS, MS without nudge, QMS q = 6, sum-product; counters / flags

@@ -142,7 +142,9 @@ class NMSDecoder:
     def supports_early_stop(self, T=None, kernel=None) -> bool:
         """Whether ``decode(..., early_stop=True)`` is served for this decoder
         (``ldpc_es_supported``): a QMS grid with q in {5, -5, 4, 3}, no per-edge check weights, kernel
-        auto or fused, and a graph that an early-stop instance of the bit-sliced kernel fits."""
+        auto or fused, and a graph that an early-stop instance of the bit-sliced kernel fits (wman,
+        802.11n) or, with channel weights that are all 1, the compressed kernel's early-stop build
+        (5G BG1 n2112)."""
         T = self.T if T is None else int(T)
         if T > self.T:
             return False

@@ -4,58 +4,89 @@
 pack-maximum iterations, the histogram and both modes' frame errors, one JSON line each and
 ``<out>/sweep_step.json``.
 
-  python tools/early_stop_step.py [out_dir]        (default: bench_out/, which git ignores)
+  python tools/early_stop_step.py [out_dir] [--points CONFIG:SNR,SNR,... ...] [--batch B]
+
+  out_dir   default bench_out/, which git ignores
+  --points  the configs (bench.py's) and their SNRs in dB; default C2:3.5,5.0,6.5 C3:4.5,6.0;
+            C5 alone: --points C5:3.0,8.0,14.5
 """
-import json, os, sys, time
+import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-import numpy as np, torch
-import bench
-from ldpc_error_floor_amd.decoder import NMSDecoder
 
-B = 1 << 20
-dev = torch.device("cuda", 0)
-rows = []
-for config, snrs in (("C2", [3.5, 5.0, 6.5]), ("C3", [4.5, 6.0])):
-    cfg = bench.CONFIGS[config]
-    proto, g, W, cp = bench.load_problem(config=config)
-    dec = NMSDecoder(proto, cfg["z"], W, 2, 5, device=dev, B_max=B)
-    assert dec.supports_early_stop()
-    for snr in snrs:
-        sigma = float(cp.sigma(snr))
-        def run(es, seed):
-            cnt = torch.zeros(4, dtype=torch.int64, device=dev)
-            kw = dict(early_stop=True, iter_hist=True, n_iter=True) if es else {}
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            r = dec.decode_awgn(B, sigma, seed, counters=cnt, **kw)
-            e1.record()
-            torch.cuda.synchronize()
-            return e0.elapsed_time(e1), r
-        out = {"config": config, "T": dec.T, "snr_db": snr}
-        for es in (False, True):
-            for w in range(2):
-                run(es, 11)
-            ts = []
-            for k in range(5):
-                t, r = run(es, 11)
-                ts.append(t)
-            tag = "es" if es else "full"
-            out[tag + "_ms"] = [round(x, 3) for x in ts]
-            out[tag + "_ms_median"] = round(float(np.median(ts)), 3)
-            out[tag + "_kernel"] = dec.last_kernel()
-            c = r.counters.cpu().numpy()
-            out[tag + "_frame_err_last"] = int(c[1]); out[tag + "_frames"] = B
-            if es:
-                h = r.iter_hist.cpu().numpy().astype(np.float64)
-                ni = r.n_iter.cpu().numpy().astype(np.int64)
-                out["mean_iter"] = round(float((h * np.arange(1, h.size + 1)).sum() / h.sum()), 3)
-                pm = ni.reshape(-1, 32).max(axis=1)
-                out["pack_max_mean"] = round(float(pm.mean()), 3)
-                out["pack_max_max"] = int(pm.max())
-                out["iter_hist"] = [int(x) for x in h]
-        print(json.dumps(out), flush=True)
-        rows.append(out)
-OUT = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "bench_out")
-os.makedirs(OUT, exist_ok=True)
-json.dump(rows, open(os.path.join(OUT, "sweep_step.json"), "w"), indent=1)
+
+def parse(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("out", nargs="?", default=os.path.join(ROOT, "bench_out"))
+    ap.add_argument("--points", nargs="+", default=["C2:3.5,5.0,6.5", "C3:4.5,6.0"], metavar="CONFIG:SNRS")
+    ap.add_argument("--batch", type=int, default=1 << 20, help="codewords per decode")
+    a = ap.parse_args(argv)
+    pts = []
+    for p in a.points:
+        config, _, snrs = p.partition(":")
+        try:
+            pts.append((config, [float(x) for x in snrs.split(",")]))
+        except ValueError:
+            ap.error(f"--points {p!r}: expected CONFIG:SNR,SNR,...")
+    a.points = pts
+    return a
+
+
+def main(argv=None):
+    a = parse(argv)
+    import numpy as np, torch
+    import bench
+    from ldpc_error_floor_amd.decoder import NMSDecoder
+    for config, _ in a.points:
+        if config not in bench.CONFIGS:
+            raise SystemExit(f"unknown config {config!r}: one of {sorted(bench.CONFIGS)}")
+    B = a.batch
+    dev = torch.device("cuda", 0)
+    rows = []
+    for config, snrs in a.points:
+        cfg = bench.CONFIGS[config]
+        proto, g, W, cp = bench.load_problem(config=config)
+        dec = NMSDecoder(proto, cfg["z"], W, 2, 5, device=dev, B_max=B)
+        dec.punct, dec.short = cfg.get("punct", (0, 0)), cfg.get("short", (0, 0))
+        assert dec.supports_early_stop(), config
+        for snr in snrs:
+            sigma = float(cp.sigma(snr))
+            def run(es, seed):
+                cnt = torch.zeros(4, dtype=torch.int64, device=dev)
+                kw = dict(early_stop=True, iter_hist=True, n_iter=True) if es else {}
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                r = dec.decode_awgn(B, sigma, seed, counters=cnt, **kw)
+                e1.record()
+                torch.cuda.synchronize()
+                return e0.elapsed_time(e1), r
+            out = {"config": config, "T": dec.T, "snr_db": snr}
+            for es in (False, True):
+                for w in range(2):
+                    run(es, 11)
+                ts = []
+                for k in range(5):
+                    t, r = run(es, 11)
+                    ts.append(t)
+                tag = "es" if es else "full"
+                out[tag + "_ms"] = [round(x, 3) for x in ts]
+                out[tag + "_ms_median"] = round(float(np.median(ts)), 3)
+                out[tag + "_kernel"] = dec.last_kernel()
+                c = r.counters.cpu().numpy()
+                out[tag + "_frame_err_last"] = int(c[1]); out[tag + "_frames"] = B
+                if es:
+                    h = r.iter_hist.cpu().numpy().astype(np.float64)
+                    ni = r.n_iter.cpu().numpy().astype(np.int64)
+                    out["mean_iter"] = round(float((h * np.arange(1, h.size + 1)).sum() / h.sum()), 3)
+                    pm = np.pad(ni, (0, -ni.size % 32)).reshape(-1, 32).max(axis=1)
+                    out["pack_max_mean"] = round(float(pm.mean()), 3)
+                    out["pack_max_max"] = int(pm.max())
+                    out["iter_hist"] = [int(x) for x in h]
+            print(json.dumps(out), flush=True)
+            rows.append(out)
+    os.makedirs(a.out, exist_ok=True)
+    json.dump(rows, open(os.path.join(a.out, "sweep_step.json"), "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()

@@ -14,6 +14,8 @@ resume at another world size is refused (the key holds the partition).  Rank 0 w
 
   python tools/sweep_c5.py --out gpurun_out/sweep_c5 [--scan 4194304] [--deep 1073741824]
   python tools/sweep_c5.py --gpus 8 --out gpurun_out/c5_deep --deep-snrs 15.0 --deep 85899345920
+  python tools/sweep_c5.py --early-stop --out bench_out/c5_es --deep-snrs 14.5   (each
+      frame stops at its first zero-syndrome iteration; C5 runs the bsc early-stop build)
 
 ``--gpus N`` (N > 1, no WORLD_SIZE in the environment): starts ranks 0..N-1 of this command as
 fresh child processes (``ldpc_error_floor_amd.launch``; never an exec); under
@@ -171,6 +173,8 @@ def main(argv=None, make_decoder=None):
                 deep_idx.append(zero[0])
         deep, t_deep = run("deep", sorted(set(deep_idx)), a.deep) if deep_idx else ([], 0.0)
         n_total = a.scan * len(scan) + a.deep * len(set(deep_idx))
+        if a.early_stop and hasattr(dec, "last_kernel"):   # (the early-stop build that served it)
+            kernel = dec.last_kernel() or kernel
         out = {"workload": workload(a.config, cfg) +
                ", on-GPU Philox AWGN (seed 1076 + 7919 x SNR in mdB, + 104729 in the deep stage, "
                "indexed by the global codeword number), all-zero codeword",
