@@ -803,6 +803,9 @@ static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const Bs
     a.target_bits = b.target_bits;
     a.cn_lanes = p.cn_lanes;
     a.cn_dmin = p.cn_dmin;
+    // the T loop's fold of the frame-error words: a wave with slack at the check barrier -- the
+    // last wave where it holds no check lanes, else wave 1 (waves 0, 4, 8, ... share a SIMD)
+    a.fold_wave = p.cn_lanes < 64 * p.nw ? (uint32_t)(p.nw - 1) : (p.nw > 1 ? 1u : 0u);
     a.inv = 1.0f / step;
     a.cu = p.cu > 0.f ? p.cu : -1.f;
     a.qmax = bs_qmax(mode);

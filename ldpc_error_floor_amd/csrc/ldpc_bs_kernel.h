@@ -116,8 +116,9 @@ struct BsArgs {
     uint32_t* hdx;               // XP builds: [T][packs][n_vars] hard decisions (bit r = codeword
                                  // 32 pack + r), the hard-bit / syndrome export
     uint32_t off_slots, off_pad, off_zero, off_red, off_alut, off_blut, off_hdz;   // LDS byte offsets
-    uint32_t pad_unused;         // unused: keeps off_ch and ablate at their offsets (without it
-                                 // the 802.11n build allocates its registers differently)
+    uint32_t fold_wave;          // (one-chunk instances) the wave that folds the frame-error
+                                 // words in the T loop: the last wave where it holds no check
+                                 // lanes, else wave 1 (bs_run)
     uint32_t off_ch;             // per-lane LDS words (one-chunk instances): the check lane's
                                  // slot base (| alpha-table address << 16), [lane]
                                  // (RED: 16 words, then T words: iteration t's frame-error word)
@@ -571,7 +572,7 @@ __device__ __forceinline__ void gen_tables(const BsGen& g, int tid, int NT) {
 // about a pack's duration on 5G BG2 (C4); bsc passes one_per_cu = false and starts at 0
 constexpr double STAGGER_US = 60.0;
 // the LDS words the variable phases OR their frame-error words into (lane & 31: two lanes per
-// word, distinct banks); wave 0 folds them at the next iteration's top
+// word, distinct banks); one wave folds them in the next iteration, before its check barrier
 constexpr int FLORW = 32;
 // The pack loop: a workgroup of a one-chunk instance without UCN (wman) decodes packs blockIdx.x,
 // blockIdx.x + gridDim.x, ... instead of one, on a grid of the workgroups that are resident at
@@ -703,7 +704,13 @@ k_bs(std::conditional_t<ES, BsArgsEs, BsArgs> a) {
         pcol[u] = __builtin_amdgcn_readfirstlane(a.vn_wdeg[3 * (u * nwv + wave) + 2]);
         tab_b[u] = (a.bcols > 1 && vv[u] >= 0) ? (uint32_t)(((UCN ? (vv[u] & 0xFFFF) : vv[u]) / (nv / a.bcols)) * BLUT_W * 4) : 0u;
     }
-    int cn_dmin = a.cn_dmin;
+    // (the pack loop's units: bit 8 marks the wave that folds the frame-error words in the T loop,
+    // a.fold_wave, carried in a word the loop holds anyway -- there the arguments are read through
+    // the pack's opaque pointer, and read at the fold the index was a scalar load and its wait on
+    // every wave, every iteration; degrees are below 256.  The other units compare a.fold_wave,
+    // which they hold in SGPRs: carrying the mark cost the 802.11n early-stop build 7 reloads.)
+    constexpr int FOLDB = BS_LOOP_TU ? 0x100 : 0;
+    int cn_dmin = a.cn_dmin | ((FOLDB && (uint32_t)wave == a.fold_wave) ? FOLDB : 0);
 
     // ---- channel planes: the lane's variables for the 32 codewords of the pack ------------------
     // (no __syncthreads_or: it allocates static LDS, which would move the dynamic LDS base
@@ -1133,7 +1140,7 @@ k_bs(std::conditional_t<ES, BsArgsEs, BsArgs> a) {
             }
         }
         // the frame-error words: every lane ORs its word into one of the FLORW LDS words, which
-        // wave 0 folds at the next iteration's top; the last iteration reduces over the wave
+        // one wave folds in the next iteration; the last iteration reduces over the wave
         // (with its APP and bit counts) and lane 0 adds the results
         if (!first && !last) {
             PH("vn_flags", 0);
@@ -1226,7 +1233,8 @@ k_bs(std::conditional_t<ES, BsArgsEs, BsArgs> a) {
     BS_ST(4);
     for (int t = 0; t < (ABL(16) ? 0 : a.T); ++t) {
         PH("top", 0);
-        if (wave == 0 && t > 0) {             // fold iteration t-1's frame flags
+        // (the one-chunk instances fold after the check phase, on a wave with slack at its barrier)
+        if (!ONE && wave == 0 && t > 0) {     // fold iteration t-1's frame flags
             // (every lane of wave 0 writes the same words: a wave-uniform branch, no thread
             // index kept live through the loop; kept in LDS for the iter_wrong export after the
             // loop: a global pointer held through it cost the 64-VGPR build 17 SGPR spill moves)
@@ -1242,6 +1250,7 @@ k_bs(std::conditional_t<ES, BsArgsEs, BsArgs> a) {
 #pragma unroll
         for (int u = 0; u < VPL; ++u) asm volatile("" : "+s"(dw[u]), "+s"(dwmin[u]));   // compared per use, not hoisted as masks
         if (!RPW) asm volatile("" : "+s"(cn_dmin));
+        const int cdm = FOLDB ? (cn_dmin & (FOLDB - 1)) : cn_dmin;    // (without the fold mark)
         // (the lane's variable made opaque per iteration on the multi-chunk instances: [v >= 0]
         // and [v < target bits] are compared per use, not held through the loop as spilled
         // 64-bit lane masks)
@@ -1317,7 +1326,7 @@ k_bs(std::conditional_t<ES, BsArgsEs, BsArgs> a) {
             // slot m of the lane: a real edge (always while LPC m + LPC - 1 < cn_dmin)
             auto real = [&](int m) __attribute__((always_inline)) -> bool {
                 if constexpr (RPW) return ((rp >> (RB * c + m)) & 1u) != 0u;
-                else return LPC * m + LPC - 1 < cn_dmin || LPC * m + cj < cdeg;
+                else return LPC * m + LPC - 1 < cdm || LPC * m + cj < cdeg;
             };
             auto caddr = [&](int m) __attribute__((always_inline)) -> uint32_t {
                 return real(m) ? cbase + m * cstride : a.off_pad;
@@ -1470,6 +1479,31 @@ k_bs(std::conditional_t<ES, BsArgsEs, BsArgs> a) {
                     for (int i = 0; i < 4; ++i) Mg[i] = mux(cand[m], q2[i], q1[i]);
                     write_slot(cbase + m * cstride, par ^ ns[m], Mg);
                 }
+            }
+        }
+        if constexpr (ONE) {
+            // fold iteration t-1's frame flags, off the check phase's critical wave: at the loop's
+            // top wave 0 ran the fold (two LDS round trips and a wave_or) before its check work,
+            // still at the variable phase's priority, and the check barrier waited for it (wman:
+            // 83 K clocks per pack against 61-74 K on the two waves sharing its SIMD).  Here one
+            // wave with slack at the check barrier folds after its own check work: the last wave
+            // where it holds no check lanes (802.11n), else wave 1 (wman: waves 1-3 share their
+            // SIMD with one other check wave, not two).
+            // The words of t-1 are complete (the variable barrier of t-1) and are zero again
+            // before any variable phase t ORs into them (the check barrier below).  RED[16 + t - 1]
+            // and RED[1] have no reader inside the loop: the early-stop block below reads the
+            // syndrome words and HD only, and both epilogues come after a barrier that follows
+            // this one.
+            const bool folds = FOLDB ? (cn_dmin & FOLDB) != 0 : (uint32_t)wave == a.fold_wave;
+            if (folds && t > 0) {
+                // (every lane writes the same words: a wave-uniform branch, no thread index kept
+                // live through the loop; kept in LDS for the iter_wrong export after the loop)
+                const uint32_t ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+                uint32_t x = ln < 32u ? RED[flor + ln] : 0u;
+                if (ln < 32u) RED[flor + ln] = 0u;
+                const uint32_t w0 = wave_or(x);
+                RED[16 + t - 1] = w0;
+                RED[1] &= w0;
             }
         }
         BS_ST(0);
