@@ -218,6 +218,40 @@ int ldpc_decode_awgn_es(ldpc_ctx* ctx, int64_t B, const ldpc_decode_params* para
    (no reference counterpart). */
 int ldpc_es_supported(const ldpc_ctx* ctx, const ldpc_decode_params* params);
 
+/* The decoded word: the hard decisions of the LAST iteration and a per-frame
+   "is not a codeword" flag, from the same launch of the bit-sliced kernels that produces the
+   counters.  No new arithmetic: for codeword b,
+     hard_last[b]   = hd_{T-1} = (APP_{T-1} >= 0) over all N*z variables, packed as
+                      hard_bits[T-1][b] is: ceil(N*z/32) words, bit v % 32 of word v / 32, the
+                      bits past N*z zero; punctured and shortened bits included
+     word_flags[b]    bit 0 = the syndrome of hard_last[b] over all M*z checks is nonzero
+     counters, frame_flags  as ldpc_decode gives them (for the all-zero codeword)
+   The only workspace is ceil(B_max/32) * N*z * 4 bytes (one word per 32 codewords and variable),
+   allocated at the first call; nothing is proportional to T.
+   Input LLRs must lie on the quantizer grid (shortened bits at +-clip_llr allowed), the rule of
+   the early-stop mode.  A pack of 32 codewords (b / 32) holding an off-grid value is not decoded:
+   word_flags = 0x80, frame_flags = 0x80, hard_last rows all zero, nothing in the counters.
+   Served: what the bit-sliced kernels decode -- QMS with q_bit 5, -5, 4 or 3, no per-edge check
+   weights, kernel AUTO or FUSED, a graph the bit-sliced kernel (bsl) or else the compressed one
+   (bsc) fits, with or without UCN weights.  Anything else (the float modes, q_bit 6, flood, graphs
+   only the v5 kernel serves) returns LDPC_ERR_UNSUPPORTED with nothing launched and nothing
+   written.  ldpc_ctx_last_kernel reports the kernel's name with ",word" inside the brackets
+   ("bsl[p32,w9,d15,v6,l4,word]").  params->outputs_size is not read.
+   size: sizeof(ldpc_word_outputs) of the caller's header; any other value -> LDPC_ERR_ARG. */
+typedef struct ldpc_word_outputs {
+    int32_t size;
+    int32_t reserved;
+    uint32_t* hard_last;        /* [B][ceil(N*z/32)], required */
+    uint8_t* word_flags;        /* [B] or NULL: bit 0 syndrome nonzero, 0x80 pack not decoded */
+    int64_t* counters;          /* [4] accumulated as ldpc_decode does, or NULL */
+    uint8_t* frame_flags;       /* [B] as ldpc_decode (0x80: pack not decoded), or NULL */
+} ldpc_word_outputs;
+
+int ldpc_decode_word(ldpc_ctx* ctx, const float* llr_dev, int64_t B, const ldpc_decode_params* params,
+                     const ldpc_word_outputs* word_outputs, void* stream);
+/* Whether ldpc_decode_word serves these parameters on this context: 1, 0, or a negative status. */
+int ldpc_word_supported(const ldpc_ctx* ctx, const ldpc_decode_params* params);
+
 /* The LLR rows ldpc_channel_awgn(B, ..., offset) would write at batch rows idx_dev[0..n) (each
    index < B, any order), into rows_dev[n][n_vars]: the same values bit for bit, generated for
    those codewords only -- the uncorrected-word sweep regenerates the few failing frames' rows

@@ -159,5 +159,17 @@ LDPC_BP_FN void clamp6(uint32_t (&T)[6], const uint32_t (&v)[SB]) {
     T[5] = mux(ovf, s, v[5]);
 }
 
+// ---- 32 x 32 bit transpose (the word mode's output kernel, ldpc_word.hip) --------------------
+// One exchange of the transpose of A[i][c] = bit c of lane i's word, 32 lanes: lane i holds x,
+// its partner i ^ j holds y, hi = [bit j of i is set]; the j x j blocks off the diagonal of every
+// 2j x 2j block change places.  After the five exchanges j = 16, 8, 4, 2, 1 (in any order) lane i
+// holds bit i of every lane's first word: B[i][c] = A[c][i].
+LDPC_BP_FN uint32_t tr32_step(uint32_t x, uint32_t y, int j, bool hi) {
+    // the bit positions whose bit j is clear
+    const uint32_t m = j == 16 ? 0x0000FFFFu : j == 8 ? 0x00FF00FFu : j == 4 ? 0x0F0F0F0Fu
+                     : j == 2 ? 0x33333333u : 0x55555555u;
+    return hi ? (((y >> j) & m) | (x & ~m)) : ((x & m) | ((y & m) << j));
+}
+
 }  // namespace bs
 }  // namespace ldpc

@@ -760,8 +760,8 @@ bool bs_q8_ok(const DevGraph& g, int mode, bool ucn, float clip, int T, bool has
 // one launch of plan p; es: the early-stop outputs (an ES instance's plan), else null
 struct EsOut { uint8_t* n_iter; int64_t* iter_hist; };
 static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const BsPlan& p, const float* llr, int mode,
-                  bool ucn, int64_t* counters, uint8_t* flags, uint32_t* bad, uint32_t* hdx, const EsOut* es,
-                  hipStream_t s) {
+                  bool ucn, int64_t* counters, uint8_t* flags, uint32_t* bad, uint32_t* hdx, bool word,
+                  const EsOut* es, hipStream_t s) {
     int st = es ? bs_graph_tables(g, p, ws.bs_es_graph, ws.bs_es_graph_inst, s)
                 : bs_graph_tables(g, p, ws.bs_graph, ws.bs_graph_inst, s);
     if (st != LDPC_OK) return st;
@@ -843,6 +843,14 @@ static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const Bs
     a.off_hdl = p.off_hdl;
     a.off_ch = p.off_ch;
     if (const char* e = getenv("LDPC_DIAG_ABLATE")) a.ablate = atoi(e);   // -DBS_DIAG builds
+    // (an export launch: BsArgsXp, the word mode's switch after the BsArgs base)
+    BsArgsXp ax{};
+    const BsArgs* ap = &a;
+    if (hdx) {
+        static_cast<BsArgs&>(ax) = a;
+        ax.word = word ? 1 : 0;
+        ap = &ax;
+    }
     const int npacks = (int)((b.B + PACK - 1) / PACK);
     // the workgroups of the instances with the pack loop (ldpc_bs_kernel.h, bs_loops): by default
     // those resident at once (asked once per context, instance and LDS size: ws.bs_resident);
@@ -864,8 +872,8 @@ static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const Bs
     static unsigned long long* dst = nullptr;
     if (!dst && hipMalloc(reinterpret_cast<void**>(&dst), 256 * 8) != hipSuccess) return LDPC_ERR_OOM;
     if (hipMemsetAsync(dst, 0, 256 * 8, s) != hipSuccess) return LDPC_ERR_HIP;
-    a.stamps = dst;
-    st = kLaunch[p.inst](a, npacks, p.nw, lds, s, b.q8 != nullptr, grid, ws.bs_resident);
+    a.stamps = ax.stamps = dst;
+    st = kLaunch[p.inst](*ap, npacks, p.nw, lds, s, b.q8 != nullptr, grid, ws.bs_resident);
     unsigned long long hst[256];
     if (st != LDPC_OK || hipMemcpyAsync(hst, dst, sizeof(hst), hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
@@ -882,15 +890,15 @@ static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const Bs
     }
     return st;
 #else
-    return kLaunch[p.inst](a, npacks, p.nw, lds, s, b.q8 != nullptr, grid, ws.bs_resident);
+    return kLaunch[p.inst](*ap, npacks, p.nw, lds, s, b.q8 != nullptr, grid, ws.bs_resident);
 #endif
 }
 
 int bs_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode,
-              bool ucn, int64_t* counters, uint8_t* flags, uint32_t* bad, uint32_t* hdx, hipStream_t s) {
+              bool ucn, int64_t* counters, uint8_t* flags, uint32_t* bad, uint32_t* hdx, bool word, hipStream_t s) {
     const BsPlan p = bs_plan(g, mode, ucn, false, b.clip, b.T);
-    if (!p.ok) return bsc_decode(g, b, ws, llr, mode, ucn, counters, flags, bad, hdx, s);
-    return bs_run(g, b, ws, p, llr, mode, ucn, counters, flags, bad, hdx, nullptr, s);
+    if (!p.ok) return bsc_decode(g, b, ws, llr, mode, ucn, counters, flags, bad, hdx, word, s);
+    return bs_run(g, b, ws, p, llr, mode, ucn, counters, flags, bad, hdx, word, nullptr, s);
 }
 
 // ---- early stop ---------------------------------------------------------------
@@ -947,7 +955,7 @@ int bs_decode_es(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const flo
     }
     if (to_bsc) return bsc_decode_es(g, b, ws, llr, mode, ucn, counters, flags, ws.bs_bad, n_iter, iter_hist, s);
     const EsOut es{n_iter, iter_hist};
-    return bs_run(g, b, ws, p, llr, mode, ucn, counters, flags, ws.bs_bad, nullptr, &es, s);
+    return bs_run(g, b, ws, p, llr, mode, ucn, counters, flags, ws.bs_bad, nullptr, false, &es, s);
 }
 
 }  // namespace ldpc

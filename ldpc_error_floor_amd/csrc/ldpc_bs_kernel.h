@@ -147,6 +147,13 @@ struct BsArgsEs : BsArgs {
     // word t = OR over the checks of the syndrome of iteration t's hard decisions)
 };
 
+// The export builds' arguments (XP): BsArgs and the word mode's switch, carried the
+// same way.
+struct BsArgsXp : BsArgs {
+    int word;                    // 1: hdx is [packs][n_vars] and takes the last iteration's hard
+                                 // decisions alone (ldpc_decode_word); 0: every iteration's
+};
+
 // the kernel's own arguments read from the kernel-argument segment (scalar loads): how the
 // early-stop statements reach their fields, also where the pack loop's units rename `a`
 template <class A>
@@ -626,9 +633,9 @@ constexpr bool bs_loops(const BsInst& k) { return k.VPL == 1 && k.CPL == 1 && !k
 template <int D, int DV, int LPC, int VPL, int CPL, bool UCN, bool BIG, bool PK, int WPE, bool XP, int LB, bool Q8,
           bool ES = false>
 __global__ void __launch_bounds__(LB) __attribute__((amdgpu_waves_per_eu(WPE)))
-k_bs(std::conditional_t<ES, BsArgsEs, BsArgs> a) {
+k_bs(std::conditional_t<ES, BsArgsEs, std::conditional_t<XP, BsArgsXp, BsArgs>> a) {
     static_assert(LPC == 2 || LPC == 4, "lanes per check");
-    using KArgs = std::conditional_t<ES, BsArgsEs, BsArgs>;
+    using KArgs = std::conditional_t<ES, BsArgsEs, std::conditional_t<XP, BsArgsXp, BsArgs>>;
     static_assert(!ES || (UCN && VPL == 1 && CPL == 1 && !XP), "early stop: one-chunk UCN-compiled instances");
     constexpr int SB = (DV * QMAX + QMAX <= 127) ? 8 : 9;     // planes of S and of lw + S
     constexpr int EPL = (D + LPC - 1) / LPC;                     // edge slots per check lane
@@ -1072,7 +1079,10 @@ k_bs(std::conditional_t<ES, BsArgsEs, BsArgs> a) {
                     if (UCN && !last && v >= 0 && (ES || ucn_on(tb))) lds_put(hda, hd);   // HD[v] (Main_Functions.py:184-188)
                     hd &= valid;                                     // APP >= 0 -> hard decision 1
                     if constexpr (XP) {                              // iteration tb - 1's hard decisions
-                        if (v >= 0) a.hdx[((size_t)(tb - 1) * (size_t)((a.B + 31) >> 5) + BS_PK) * nv + v] = hd;
+                        // (word mode, wave-uniform: the last iteration's alone, one row per pack)
+                        const bool word = kern_args<KArgs>().word != 0;
+                        const size_t row = word ? (size_t)BS_PK : (size_t)(tb - 1) * (size_t)((a.B + 31) >> 5) + BS_PK;
+                        if (v >= 0 && (last || !word)) a.hdx[row * nv + v] = hd;
                     }
                     if (ABL(8)) hd = 0u;
                     if (counted) {
@@ -1711,7 +1721,9 @@ int launch_bs_x(const BsArgs& a, int npacks, int nw, size_t lds, hipStream_t s, 
         }
         if (grid > 0 && grid < npacks) nblocks = grid;
     }
-    hipLaunchKernelGGL(fn, dim3(nblocks), dim3(64 * nw), lds, s, a);
+    // (an export launch is handed BsArgsXp, passed as its BsArgs base: bs_run)
+    if constexpr (XP) hipLaunchKernelGGL(fn, dim3(nblocks), dim3(64 * nw), lds, s, static_cast<const BsArgsXp&>(a));
+    else hipLaunchKernelGGL(fn, dim3(nblocks), dim3(64 * nw), lds, s, a);
     return hipGetLastError() == hipSuccess ? LDPC_OK : LDPC_ERR_HIP;
 }
 template <int I>

@@ -75,6 +75,12 @@ struct BscArgs {
     BsGen gen;                   // Q8 builds: the in-prologue channel (bsl's; tables at SGN)
 };
 
+// The export builds' arguments (XP): BscArgs and the word mode's switch (as bsl's
+// BsArgsXp).
+struct BscArgsXp : BscArgs {
+    int word;                    // 1: hdx is [packs][n_vars], the last iteration's hard decisions alone
+};
+
 // The early-stop builds' arguments: BscArgs and what the mode adds, so the other
 // builds' kernel arguments stay as they are.
 struct BscArgsEs : BscArgs {
@@ -111,7 +117,7 @@ __device__ __forceinline__ void lds_dput(uint32_t addr, uint32_t x, uint32_t y) 
 template <int D, int DVH, int DVL, int LPC, int VPL, int CPL, int WPE, bool XP, int LB, bool MIX, bool B1, bool Q8,
           bool ES = false>
 __global__ void __launch_bounds__(LB) __attribute__((amdgpu_waves_per_eu(WPE)))
-k_bsc(std::conditional_t<ES, BscArgsEs, BscArgs> a) {
+k_bsc(std::conditional_t<ES, BscArgsEs, std::conditional_t<XP, BscArgsXp, BscArgs>> a) {
     static_assert(!ES || (B1 && !XP), "early stop: the beta = 1 build, no export");
     constexpr int SB = (DVH * QMAX + QMAX <= 127) ? 8 : 9;
     constexpr int EPL = (D + LPC - 1) / LPC;
@@ -306,7 +312,9 @@ k_bsc(std::conditional_t<ES, BscArgsEs, BscArgs> a) {
                     }
                     hd &= valid;
                     if constexpr (XP) {                              // iteration tb - 1's hard decisions
-                        if (v >= 0) a.hdx[((size_t)(tb - 1) * (size_t)((a.B + 31) >> 5) + blockIdx.x) * nv + v] = hd;
+                        // (word mode, wave-uniform: the last iteration's alone, one row per pack)
+                        const size_t row = a.word ? (size_t)blockIdx.x : (size_t)(tb - 1) * (size_t)((a.B + 31) >> 5) + blockIdx.x;
+                        if (v >= 0 && (last || !a.word)) a.hdx[row * nv + v] = hd;
                     }
                     if (counted) {
                         wr |= hd;
@@ -998,7 +1006,9 @@ static int bsc_launch1(const BscArgs& a, int nblocks, int nw, size_t lds, hipStr
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)BS_LDS_MAX);
         attr = true;
     }
-    hipLaunchKernelGGL(fn, dim3(nblocks), dim3(64 * nw), lds, s, a);
+    // (an export launch is handed BscArgsXp, passed as its BscArgs base: bsc_run)
+    if constexpr (XP) hipLaunchKernelGGL(fn, dim3(nblocks), dim3(64 * nw), lds, s, static_cast<const BscArgsXp&>(a));
+    else hipLaunchKernelGGL(fn, dim3(nblocks), dim3(64 * nw), lds, s, a);
     return hipGetLastError() == hipSuccess ? LDPC_OK : LDPC_ERR_HIP;
 }
 template <int I, bool XP>
@@ -1140,7 +1150,7 @@ const char* bsc_es_kernel_name(const DevGraph& g, int mode, bool ucn, bool per_e
 // one launch of plan p; es: the early-stop outputs (an early-stop plan), else null
 struct BscEsOut { uint8_t* n_iter; int64_t* iter_hist; };
 static int bsc_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const BscPlan& p, const float* llr, int mode,
-                   int64_t* counters, uint8_t* flags, uint32_t* bad, uint32_t* hdx, const BscEsOut* es,
+                   int64_t* counters, uint8_t* flags, uint32_t* bad, uint32_t* hdx, bool word, const BscEsOut* es,
                    hipStream_t s) {
     // (the graph tables do not depend on the mode: both kinds of decode share them)
     int st = bsc_tables(g, p, ws, s);
@@ -1222,20 +1232,26 @@ static int bsc_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const B
             default: return LDPC_ERR_UNSUPPORTED;
         }
     }
+    // (an export launch: BscArgsXp, the word mode's switch after the BscArgs base)
+    BscArgsXp ax{};
+    if (hdx) {
+        static_cast<BscArgs&>(ax) = a;
+        ax.word = word ? 1 : 0;
+    }
     switch (p.inst) {
-        case 1: return hdx ? bsc_launch<1, true>(a, nblocks, p.nw, p.lds, s, q8) : bsc_launch<1, false>(a, nblocks, p.nw, p.lds, s, q8);
-        case 2: return hdx ? bsc_launch<2, true>(a, nblocks, p.nw, p.lds, s, q8) : bsc_launch<2, false>(a, nblocks, p.nw, p.lds, s, q8);
-        case 3: return hdx ? bsc_launch<3, true>(a, nblocks, p.nw, p.lds, s, q8) : bsc_launch<3, false>(a, nblocks, p.nw, p.lds, s, q8);
-        case 4: return hdx ? bsc_launch<4, true>(a, nblocks, p.nw, p.lds, s, q8) : bsc_launch<4, false>(a, nblocks, p.nw, p.lds, s, q8);
-        default: return hdx ? bsc_launch<0, true>(a, nblocks, p.nw, p.lds, s, q8) : bsc_launch<0, false>(a, nblocks, p.nw, p.lds, s, q8);
+        case 1: return hdx ? bsc_launch<1, true>(ax, nblocks, p.nw, p.lds, s, q8) : bsc_launch<1, false>(a, nblocks, p.nw, p.lds, s, q8);
+        case 2: return hdx ? bsc_launch<2, true>(ax, nblocks, p.nw, p.lds, s, q8) : bsc_launch<2, false>(a, nblocks, p.nw, p.lds, s, q8);
+        case 3: return hdx ? bsc_launch<3, true>(ax, nblocks, p.nw, p.lds, s, q8) : bsc_launch<3, false>(a, nblocks, p.nw, p.lds, s, q8);
+        case 4: return hdx ? bsc_launch<4, true>(ax, nblocks, p.nw, p.lds, s, q8) : bsc_launch<4, false>(a, nblocks, p.nw, p.lds, s, q8);
+        default: return hdx ? bsc_launch<0, true>(ax, nblocks, p.nw, p.lds, s, q8) : bsc_launch<0, false>(a, nblocks, p.nw, p.lds, s, q8);
     }
 }
 
 int bsc_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode,
-               bool ucn, int64_t* counters, uint8_t* flags, uint32_t* bad, uint32_t* hdx, hipStream_t s) {
+               bool ucn, int64_t* counters, uint8_t* flags, uint32_t* bad, uint32_t* hdx, bool word, hipStream_t s) {
     const BscPlan p = bsc_plan(g, mode, ucn, false, b.clip, b.T);
     if (!p.ok) return LDPC_ERR_UNSUPPORTED;
-    return bsc_run(g, b, ws, p, llr, mode, counters, flags, bad, hdx, nullptr, s);
+    return bsc_run(g, b, ws, p, llr, mode, counters, flags, bad, hdx, word, nullptr, s);
 }
 
 // the early-stop decode (as bs_decode_es, which falls through to it): LDPC_ERR_UNSUPPORTED with
@@ -1248,7 +1264,7 @@ int bsc_decode_es(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const fl
     if (b.q8 && !bsc_es_q8_ok(g, mode, ucn, b.clip, b.T, reinterpret_cast<const AwgnParams*>(b.gen8)->ss > 0))
         return LDPC_ERR_UNSUPPORTED;
     const BscEsOut es{n_iter, iter_hist};
-    return bsc_run(g, b, ws, p, llr, mode, counters, flags, bad, nullptr, &es, s);
+    return bsc_run(g, b, ws, p, llr, mode, counters, flags, bad, nullptr, false, &es, s);
 }
 
 }  // namespace ldpc

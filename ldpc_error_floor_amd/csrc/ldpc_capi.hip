@@ -810,6 +810,61 @@ int ldpc_decode_awgn_es(ldpc_ctx* c, int64_t B, const ldpc_decode_params* p, con
     return decode_es_impl(c, c->llr_scratch, B, p, o, stream, nullptr, nullptr);
 }
 
+// ---- decoded word (include/ldpc_nms.h) ------------------------------------------
+// the request's mode when the bit-sliced kernels decode it, LDPC_ERR_UNSUPPORTED when they do
+// not, or the status of a bad request (no device call)
+static int word_request(const ldpc_ctx* c, int64_t B, const ldpc_decode_params* p, int* mode) {
+    const ldpc_graph* g = c->g;
+    if (!g->d_alpha || !g->d_beta) return LDPC_ERR_STATE;
+    const int chk = host::check_decode(g->h, B, c->B_max, c->T_max, g->T_w, p, mode);
+    if (chk != LDPC_OK) return chk;
+    if (p->kernel != LDPC_KERNEL_AUTO && p->kernel != LDPC_KERNEL_FUSED)
+        return p->kernel == LDPC_KERNEL_FLOOD ? LDPC_ERR_UNSUPPORTED : LDPC_ERR_ARG;
+    if (p->decoding_type != LDPC_DEC_QMS || g->per_edge_w ||
+        !fused_word_supported(g->dev, *mode, p->T, p->clip_llr, g->d_alpha_ucn != nullptr, false))
+        return LDPC_ERR_UNSUPPORTED;
+    return LDPC_OK;
+}
+
+int ldpc_word_supported(const ldpc_ctx* c, const ldpc_decode_params* p) {
+    if (!c || !p) return LDPC_ERR_ARG;
+    int mode = -1;
+    const int st = word_request(c, 1, p, &mode);
+    return st == LDPC_OK ? 1 : st == LDPC_ERR_UNSUPPORTED ? 0 : st;
+}
+
+int ldpc_decode_word(ldpc_ctx* c, const float* llr_dev, int64_t B, const ldpc_decode_params* p,
+                     const ldpc_word_outputs* o, void* stream) {
+    if (!c || !llr_dev || !p || !o || o->size != (int32_t)sizeof(ldpc_word_outputs) || !o->hard_last)
+        return LDPC_ERR_ARG;
+    int mode = -1;
+    const int rq = word_request(c, B, p, &mode);
+    if (rq != LDPC_OK) return rq;
+    ldpc_graph* g = c->g;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    DeviceGuard dg(g->device);
+    const bool ucn = g->d_alpha_ucn != nullptr;
+    Bufs b{};
+    b.B = B;
+    b.ntiles = (int)((B + TILE - 1) / TILE);
+    b.T = p->T;
+    b.n_vars = g->h.N * g->h.z;
+    b.target_bits = p->target_bits;
+    b.clip = p->clip_llr;
+    b.alpha = g->d_alpha;
+    b.alpha_ucn = g->d_alpha_ucn;
+    b.beta = g->d_beta;
+    b.count = 1;
+    const int st = fused_decode_word(g->dev, b, c->fused, llr_dev, mode, ucn, c->B_max, o->counters,
+                                     o->frame_flags, o->hard_last, o->word_flags, s);
+    if (st != LDPC_OK) return st;
+    // the kernel's usual name with ",word" inside the brackets
+    const char* nm = bs_kernel_name(g->dev, mode, ucn, false, p->clip_llr, p->T);
+    const size_t n = std::strlen(nm);
+    std::snprintf(c->last_kernel, sizeof(c->last_kernel), "%.*s,word]", (int)(n ? n - 1 : 0), nm);
+    return hipGetLastError() == hipSuccess ? LDPC_OK : LDPC_ERR_HIP;
+}
+
 int ldpc_ctx_last_kernel(const ldpc_ctx* c, char* name, int32_t name_len) {
     if (!c || !name || name_len <= 0) return LDPC_ERR_ARG;
     std::strncpy(name, c->last_kernel, (size_t)name_len - 1);

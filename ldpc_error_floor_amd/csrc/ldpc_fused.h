@@ -24,6 +24,8 @@ struct FusedWorkspace {
     uint32_t* hdx = nullptr;       // [T][packs][n_vars] bit-sliced hard decisions (bit export of
     int64_t hdx_elems = 0;         // the bit-sliced kernels; fixup packs are in `hd` instead)
     bool bits_packed = false;      // the last bit-exporting decode wrote hdx (+ hd for bad packs)
+    uint32_t* hdw = nullptr;       // [ceil(B_max / 32)][n_vars] the word mode's last-iteration hard
+    int64_t hdw_elems = 0;         // decisions, bit-sliced (allocated on first use)
     const char* last_kernel = "";  // the kernel that served the last decode (ldpc_ctx_last_kernel)
     // what the per-decode table kernels last wrote (they depend only on the graph, the weights
     // and T): a decode with the same key skips them
@@ -62,9 +64,11 @@ int fused5_cw(const DevGraph& g, int T);
 bool bs_supported(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T);
 const char* bs_kernel_name(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T);
 // hdx: null, or [T][packs][n_vars] u32: also store every iteration's hard decisions (bit r of
-// word (t, pack, v) = codeword 32 pack + r; the export build of the kernel)
+// word (t, pack, v) = codeword 32 pack + r; the export build of the kernel).  word:
+// hdx is [packs][n_vars] and takes the last iteration's hard decisions alone
 int bs_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode,
-              bool ucn, int64_t* counters, uint8_t* flags, uint32_t* bad, uint32_t* hdx, hipStream_t s);
+              bool ucn, int64_t* counters, uint8_t* flags, uint32_t* bad, uint32_t* hdx, bool word,
+              hipStream_t s);
 // the in-prologue channel (Bufs::q8 / gen8) serves this counters-only decode: the bit-sliced
 // kernel applies, has room for the sampler's tables in its slot region and, with shortened bits
 // in the channel, has the shortened-bit marker (a BIG instance)
@@ -94,7 +98,8 @@ bool fused_awgn_v5(const DevGraph& g, int mode, int T, float clip, bool ucn, boo
 bool bsc_supported(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T);
 const char* bsc_kernel_name(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T);
 int bsc_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode,
-               bool ucn, int64_t* counters, uint8_t* flags, uint32_t* bad, uint32_t* hdx, hipStream_t s);
+               bool ucn, int64_t* counters, uint8_t* flags, uint32_t* bad, uint32_t* hdx, bool word,
+               hipStream_t s);
 // its early-stop builds: the beta = 1 build of the mixed-lane instances (bs_*_es fall through to
 // these where bs_decode falls through to bsc_decode); kernel name "bsc[...,es]"
 bool bsc_es_supported(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T);
@@ -103,6 +108,19 @@ const char* bsc_es_kernel_name(const DevGraph& g, int mode, bool ucn, bool per_e
 int bsc_decode_es(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode, bool ucn,
                   int64_t* counters, uint8_t* flags, uint32_t* bad, uint8_t* n_iter, int64_t* iter_hist,
                   hipStream_t s);
+// the word mode (ldpc_decode_word): the request is one the bit-sliced kernels decode
+// (fused_decode would take bs_decode for its counters); the decode -- the export build storing
+// the last iteration's hard decisions alone into ws.hdw, no v5 fixup, then word_out --; and the
+// output kernel (ldpc_word.hip): hard_last [B][ceil(n_vars / 32)], word_flags [B] or null (bit 0:
+// syndrome nonzero), and, for the packs the decode marked off the grid (bad), zero rows and 0x80
+// in word_flags and frame_flags (or null)
+constexpr int WORD_MAX_VARS = 4096;      // (the bit-sliced plans' bound: 4 variables on 1024 lanes)
+bool fused_word_supported(const DevGraph& g, int mode, int T, float clip, bool ucn, bool per_edge_w);
+int fused_decode_word(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode, bool ucn,
+                      int64_t B_max, int64_t* counters, uint8_t* flags, uint32_t* hard_last,
+                      uint8_t* word_flags, hipStream_t s);
+int word_out(const DevGraph& g, const uint32_t* planes, const uint32_t* bad, int64_t B, uint32_t* hard_last,
+             uint8_t* word_flags, uint8_t* frame_flags, hipStream_t s);
 void fused_free(FusedWorkspace& ws);
 
 // float-mode fused decoder (ldpc_ffl.hip): MS, MS without nudge, QMS q = 6, sum-product; counters / flags

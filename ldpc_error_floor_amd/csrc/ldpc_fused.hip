@@ -145,7 +145,7 @@ int fused_decode(const DevGraph& g, Bufs& b, FusedWorkspace& ws, const float* ll
             }
             ws.bs_bad_n = n;
         }
-        int st = bs_decode(g, b, ws, llr, mode, ucn, counters, flags, ws.bs_bad, hdx, s);
+        int st = bs_decode(g, b, ws, llr, mode, ucn, counters, flags, ws.bs_bad, hdx, false, s);
         if (st != LDPC_OK) return st;
         ws.last_kernel = fused_kernel_name(g, mode, b.T, b.clip, ucn, per_edge_w != 0);
         ws.bits_packed = want_bits;
@@ -161,6 +161,42 @@ int fused_decode(const DevGraph& g, Bufs& b, FusedWorkspace& ws, const float* ll
     ws.last_kernel = fused5_shape_name(g, b.T);
     return fused5_decode(g, b, ws, llr, mode_qmax(mode), step, cu, per_edge_w != 0, hd_out,
                          counters, flags, s);
+}
+
+bool fused_word_supported(const DevGraph& g, int mode, int T, float clip, bool ucn, bool per_edge_w) {
+    return fused_supported(g, mode, T, clip) && g.n_vars <= WORD_MAX_VARS && use_bs(g, mode, T, ucn, per_edge_w, clip);
+}
+
+int fused_decode_word(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode, bool ucn,
+                      int64_t B_max, int64_t* counters, uint8_t* flags, uint32_t* hard_last,
+                      uint8_t* word_flags, hipStream_t s) {
+    if (!fused_word_supported(g, mode, b.T, b.clip, ucn, false)) return LDPC_ERR_UNSUPPORTED;
+    // the scratch: one word per (pack, variable) of the largest batch, whatever T is
+    const int64_t npk_max = (B_max + 31) / 32, n = npk_max * g.n_vars;
+    if (n > ws.hdw_elems) {
+        if (ws.hdw) (void)hipFree(ws.hdw);
+        ws.hdw = nullptr;
+        ws.hdw_elems = 0;
+        if (hipMalloc(reinterpret_cast<void**>(&ws.hdw), (size_t)n * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            return LDPC_ERR_OOM;
+        }
+        ws.hdw_elems = n;
+    }
+    if (npk_max > ws.bs_bad_n) {         // (the kernel's per-pack off-grid word, as fused_decode's)
+        if (ws.bs_bad) (void)hipFree(ws.bs_bad);
+        ws.bs_bad = nullptr;
+        ws.bs_bad_n = 0;
+        if (hipMalloc(reinterpret_cast<void**>(&ws.bs_bad), (size_t)npk_max * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            return LDPC_ERR_OOM;
+        }
+        ws.bs_bad_n = npk_max;
+    }
+    // (off-grid packs are marked by word_out, not decoded: no v5 fixup, so none of its tile buffers)
+    const int st = bs_decode(g, b, ws, llr, mode, ucn, counters, flags, ws.bs_bad, ws.hdw, true, s);
+    if (st != LDPC_OK) return st;
+    return word_out(g, ws.hdw, ws.bs_bad, b.B, hard_last, word_flags, flags, s);
 }
 
 HdView fused_bits_view(const FusedWorkspace& ws) {
@@ -194,6 +230,9 @@ void fused_free(FusedWorkspace& ws) {
     ws.hdx = nullptr;
     ws.hdx_elems = 0;
     ws.bits_packed = false;
+    if (ws.hdw) (void)hipFree(ws.hdw);
+    ws.hdw = nullptr;
+    ws.hdw_elems = 0;
     ws.key_gad[0] = ws.key_qtab[0] = ws.key_bslut[0] = ~0ull;
 }
 

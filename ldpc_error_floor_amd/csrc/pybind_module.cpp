@@ -217,6 +217,41 @@ PYBIND11_MODULE(_ldpc_nms, m) {
         },
         py::arg("ctx"), py::arg("T"), py::arg("decoding_type"), py::arg("q_bit"),
         py::arg("target_bits"), py::arg("kernel"), py::arg("clip_llr") = 20.0f);
+    // decoded word (ldpc_decode_word / ldpc_word_supported)
+    m.def(
+        "decode_word",
+        [](Ctx& c, uintptr_t llr, int64_t B, int T, int decoding_type, int q_bit, int target_bits,
+           float clip, int kernel, uintptr_t hard_last, uintptr_t word_flags, uintptr_t counters,
+           uintptr_t flags, uintptr_t stream) {
+            ldpc_decode_params p = make_params(T, decoding_type, q_bit, target_bits, clip, kernel);
+            ldpc_word_outputs o{};
+            o.size = (int32_t)sizeof(ldpc_word_outputs);
+            o.hard_last = reinterpret_cast<uint32_t*>(hard_last);
+            o.word_flags = reinterpret_cast<uint8_t*>(word_flags);
+            o.counters = reinterpret_cast<int64_t*>(counters);
+            o.frame_flags = reinterpret_cast<uint8_t*>(flags);
+            int st;
+            {
+                py::gil_scoped_release nogil;
+                st = ldpc_decode_word(c.h, reinterpret_cast<const float*>(llr), B, &p, &o,
+                                      reinterpret_cast<void*>(stream));
+            }
+            check(st, "ldpc_decode_word");
+        },
+        py::arg("ctx"), py::arg("llr"), py::arg("B"), py::arg("T"), py::arg("decoding_type"),
+        py::arg("q_bit"), py::arg("target_bits"), py::arg("clip"), py::arg("kernel"),
+        py::arg("hard_last"), py::arg("word_flags") = 0, py::arg("counters") = 0, py::arg("flags") = 0,
+        py::arg("stream") = 0);
+    m.def(
+        "word_supported",
+        [](Ctx& c, int T, int decoding_type, int q_bit, int target_bits, int kernel, float clip) {
+            ldpc_decode_params p = make_params(T, decoding_type, q_bit, target_bits, clip, kernel);
+            const int st = ldpc_word_supported(c.h, &p);
+            check(st, "ldpc_word_supported");
+            return st == 1;
+        },
+        py::arg("ctx"), py::arg("T"), py::arg("decoding_type"), py::arg("q_bit"),
+        py::arg("target_bits"), py::arg("kernel"), py::arg("clip_llr") = 20.0f);
     m.def(
         "channel_awgn",
         [](uintptr_t llr, int64_t B, int n_vars, double sigma, uint64_t seed, int64_t offset,

@@ -36,6 +36,10 @@ class DecodeResult:
     n_iter: Optional["object"] = None       # early stop: torch uint8 [B], iterations run (0: the
                                             # frame's pack held an off-grid LLR and was not decoded)
     iter_hist: Optional["object"] = None    # early stop: torch int64 [T], frames with n_iter == t+1
+    hard_last: Optional["object"] = None    # word mode: torch int32 [B, ceil(N*z/32)], the last
+                                            # iteration's hard decisions (``unpack_bits`` unpacks them)
+    word_flags: Optional["object"] = None   # word mode: torch uint8 [B], bit 0 = syndrome nonzero,
+                                            # 0x80 = the frame's pack held an off-grid LLR (not decoded)
 
     def frame_errors(self, B: int) -> np.ndarray:
         """``iter_wrong`` unpacked on the host: bool [T, B] (calc_ber_fer's per-iteration frame
@@ -152,6 +156,69 @@ class NMSDecoder:
         return bool(self._ext.es_supported(ctx, T, self.decoding_type, self.q_bit, self.target_bits,
                                            KERNELS[kernel or self.kernel], self.clip))
 
+    def supports_hard_last(self, T=None, kernel=None) -> bool:
+        """Whether ``decode(..., hard_last=True)`` is served for this decoder
+        (``ldpc_word_supported``): what the bit-sliced kernels decode -- a QMS grid with q in
+        {5, -5, 4, 3}, no per-edge check weights, kernel auto or fused, and a graph the bit-sliced
+        kernel or the compressed one fits."""
+        T = self.T if T is None else int(T)
+        if T > self.T:
+            return False
+        ctx = self._ensure_ctx(1, T)
+        return bool(self._ext.word_supported(ctx, T, self.decoding_type, self.q_bit, self.target_bits,
+                                             KERNELS[kernel or self.kernel], self.clip))
+
+    def _decode_word(self, llr, T, nt, hard_last, word_flags, counters, flags, kernel, stream, on_off_grid):
+        """``decode(hard_last=...)``: the decoded words of the last iteration."""
+        torch = self._torch
+        dev = self.device
+        if on_off_grid not in ("raise", "mark"):
+            raise ValueError("on_off_grid must be 'raise' or 'mark'")
+        llr = self._as_llr(llr)
+        B = int(llr.shape[0])
+        nw = (self.n_vars + 31) // 32
+        res = DecodeResult()
+        if isinstance(hard_last, torch.Tensor):             # caller-owned int32 [>= B, nw]
+            if (hard_last.dtype != torch.int32 or hard_last.device != dev or hard_last.dim() != 2 or
+                    hard_last.shape[0] < B or hard_last.shape[1] != nw or not hard_last.is_contiguous()):
+                raise ValueError(f"hard_last must be a contiguous int32 [>= B, {nw}] tensor on the decoder's device")
+            res.hard_last = hard_last
+        else:
+            res.hard_last = torch.empty((B, nw), dtype=torch.int32, device=dev)
+        want_wf = word_flags or on_off_grid == "raise"
+        if want_wf:
+            res.word_flags = torch.empty(B, dtype=torch.uint8, device=dev)
+        if counters is True:
+            counters = torch.zeros(4, dtype=torch.int64, device=dev)
+        if counters is not None:
+            if counters.dtype != torch.int64 or counters.numel() < 4 or counters.device != dev:
+                raise ValueError("counters must be an int64[4] tensor on the decoder's device")
+            res.counters = counters
+        if isinstance(flags, torch.Tensor):
+            if flags.dtype != torch.uint8 or flags.device != dev or flags.numel() < B:
+                raise ValueError("flags tensor must be uint8 on the decoder's device, >= B long")
+            res.flags = flags
+        elif flags:
+            res.flags = torch.empty(B, dtype=torch.uint8, device=dev)
+        if B == 0:
+            return res
+        ctx = self._ensure_ctx(B, T)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        ptr = lambda t: 0 if t is None else t.data_ptr()   # noqa: E731
+        self._ext.decode_word(ctx, llr.data_ptr(), B, T, self.decoding_type, self.q_bit, nt, self.clip,
+                              KERNELS[kernel or self.kernel], res.hard_last.data_ptr(), ptr(res.word_flags),
+                              ptr(res.counters), ptr(res.flags), stream.cuda_stream)
+        if on_off_grid == "raise":
+            stream.synchronize()
+            nbad = int((res.word_flags == 0x80).sum().item())
+            if nbad:
+                raise ValueError(f"hard_last: {nbad} frames are in packs with LLRs off the quantizer "
+                                 "grid and were not decoded (on_off_grid='mark' returns them marked)")
+            if not word_flags:
+                res.word_flags = None
+        return res
+
     def _es_outputs(self, res, B, T, counters, flags, n_iter, iter_hist):
         """The early-stop decode's output tensors into ``res`` (caller-owned ones checked)."""
         torch = self._torch
@@ -190,7 +257,7 @@ class NMSDecoder:
                synd: bool = False, counters=None, flags: bool = False, kernel: Optional[str] = None,
                stream=None, target_bits: Optional[int] = None, iter_wrong: bool = False,
                early_stop: bool = False, n_iter: bool = False, iter_hist=None,
-               on_off_grid: str = "raise") -> DecodeResult:
+               on_off_grid: str = "raise", hard_last=False, word_flags: bool = False) -> DecodeResult:
         """Decode a batch.  ``counters`` may be a caller-owned int64[4] device tensor that is
         accumulated into (``+=``); pass ``True`` to get a fresh one.  ``target_bits``
         overrides the output / FER bit range (default Nt*z).  ``iter_wrong``: the per-iteration
@@ -206,12 +273,30 @@ class NMSDecoder:
         served and raise ``ValueError``.  The LLRs must lie on the quantizer grid: a pack of 32
         frames holding an off-grid value is not decoded (``n_iter`` 0, ``flags`` 0x80, not
         counted); ``on_off_grid="raise"`` synchronises and raises ``ValueError`` when there is one,
-        ``"mark"`` returns the result as it is."""
+        ``"mark"`` returns the result as it is.
+
+        ``hard_last`` (``True``, or a caller-owned contiguous int32 tensor with at least B rows of
+        ceil(N*z/32) words): the decoded words -- the last iteration's hard decisions
+        over all N*z variables, packed as ``hard[T-1]`` is -- from the bit-sliced kernels' own
+        launch, with ``counters`` / ``flags`` as a plain decode gives them and, with
+        ``word_flags=True``, a uint8 [B] whose bit 0 says the word's syndrome is nonzero.  ``app``
+        defaults to False; ``app`` / ``hard`` / ``synd`` / ``iter_wrong`` / ``early_stop`` are not
+        served with it and raise ``ValueError``.  The LLRs must lie on the quantizer grid, as for
+        ``early_stop``: a pack of 32 frames holding an off-grid value is not decoded (zero rows,
+        ``word_flags`` and ``flags`` 0x80, not counted); ``on_off_grid`` as above."""
         torch = self._torch
         T = self.T if T is None else int(T)
         nt = self.target_bits if target_bits is None else int(target_bits)
         if T > self.T:
             raise ValueError(f"T={T} exceeds the {self.T} iterations the weights cover")
+        if hard_last is not False and hard_last is not None:
+            bad = [k for k, v in dict(app=app, hard=hard, synd=synd, iter_wrong=iter_wrong, early_stop=early_stop,
+                                      n_iter=n_iter, iter_hist=iter_hist is not None and iter_hist is not False).items() if v]
+            if bad:
+                raise ValueError("hard_last serves word_flags, counters and flags only, not " + ", ".join(bad))
+            return self._decode_word(llr, T, nt, hard_last, word_flags, counters, flags, kernel, stream, on_off_grid)
+        if word_flags:
+            raise ValueError("word_flags is an output of hard_last=True")
         if early_stop:
             self._es_check_exports(app=app, hard=hard, synd=synd, iter_wrong=iter_wrong)
             if on_off_grid not in ("raise", "mark"):
@@ -320,12 +405,16 @@ class NMSDecoder:
     def decode_awgn(self, B: int, sigma: float, seed: int, offset: int = 0, punct=None, short=None,
                     T: Optional[int] = None, app: bool = False, counters=None, flags=None,
                     kernel: Optional[str] = None, stream=None, iter_wrong: bool = False,
-                    early_stop: bool = False, n_iter: bool = False, iter_hist=None) -> DecodeResult:
+                    early_stop: bool = False, n_iter: bool = False, iter_hist=None,
+                    hard_last=False) -> DecodeResult:
         """Decode B codewords whose LLRs come from the on-GPU AWGN channel, generated inside
         the decoder (``ldpc_decode_awgn``): identical to ``decode(awgn(...))`` without the
         LLRs ever being written to HBM.  ``counters`` / ``flags`` as in ``decode``;
         ``early_stop`` / ``n_iter`` / ``iter_hist`` as in ``decode`` (the generated channel is
-        always on the grid)."""
+        always on the grid).  ``hard_last`` is not served here (the kernels' in-prologue channel
+        has no export build) and raises ``ValueError``: compose ``awgn()`` and ``decode()``."""
+        if hard_last is not False and hard_last is not None:
+            raise ValueError("decode_awgn does not serve hard_last: use decode(awgn(...), hard_last=True)")
         torch = self._torch
         T = self.T if T is None else int(T)
         punct = getattr(self, "punct", (0, 0)) if punct is None else punct
