@@ -252,6 +252,48 @@ int ldpc_decode_word(ldpc_ctx* ctx, const float* llr_dev, int64_t B, const ldpc_
 /* Whether ldpc_decode_word serves these parameters on this context: 1, 0, or a negative status. */
 int ldpc_word_supported(const ldpc_ctx* ctx, const ldpc_decode_params* params);
 
+/* The decoded word of the early-stop decode (no reference counterpart): what a
+   practical decoder returns, the hard decisions of the iteration the frame stopped at.  With
+   stop(b), n_iter(b) and hd_t as the early-stop mode above defines them, for codeword b
+     hard_stop[b]   = hd_{stop(b)} = (APP_{stop(b)} >= 0) over all N*z variables, punctured and
+                      shortened bits included, packed as hard_last / hard_bits[t][b] are:
+                      ceil(N*z/32) words, bit v % 32 of word v / 32, the bits past N*z zero.
+                      Frozen at stop(b), whatever later iterations do, and independent of which
+                      frames share the pack or batch.
+     word_flags[b]    bit 0 = the syndrome of hard_stop[b] over all M*z checks is nonzero: 0 for
+                      every frame with n_iter < T (the stop rule), [s_{T-1} != 0] when n_iter == T
+     counters[0..2], frame_flags, n_iter, iter_hist   exactly ldpc_decode_es's for the same input
+   A pack of 32 codewords holding an off-grid value is not decoded: word_flags = 0x80,
+   frame_flags = 0x80, n_iter = 0, hard_stop rows all zero, nothing in the counters or histogram.
+   The only workspace is ldpc_decode_word's, ceil(B_max/32) * N*z * 4 bytes, shared with it.
+   Served: exactly what ldpc_es_supported serves; ldpc_decode_awgn_es_word is identical to
+   ldpc_channel_awgn followed by ldpc_decode_es_word and generates the channel inside the kernel
+   where ldpc_decode_awgn_es does.  Anything else returns LDPC_ERR_UNSUPPORTED with nothing
+   launched and nothing written.  ldpc_ctx_last_kernel reports "bsl[...,es,word]" or
+   "bsc[...,es,word]" (and "+gen").  params->outputs_size is not read.
+   size: sizeof(ldpc_es_word_outputs) of the caller's header; any other value -> LDPC_ERR_ARG, as
+   is a NULL hard_stop; both are checked before the context is read. */
+typedef struct ldpc_es_word_outputs {
+    int32_t size;
+    int32_t reserved;
+    uint32_t* hard_stop;        /* [B][ceil(N*z/32)], required */
+    uint8_t* word_flags;        /* [B] or NULL: bit 0 syndrome nonzero, 0x80 pack not decoded */
+    int64_t* counters;          /* [4], elements 0..2 accumulated, or NULL */
+    uint8_t* frame_flags;       /* [B] or NULL */
+    uint8_t* n_iter;            /* [B] or NULL */
+    int64_t* iter_hist;         /* [T] accumulated, or NULL */
+    uint64_t reserved1;         /* not read; pads the struct to 64 bytes */
+} ldpc_es_word_outputs;
+
+int ldpc_decode_es_word(ldpc_ctx* ctx, const float* llr_dev, int64_t B, const ldpc_decode_params* params,
+                        const ldpc_es_word_outputs* outputs, void* stream);
+int ldpc_decode_awgn_es_word(ldpc_ctx* ctx, int64_t B, const ldpc_decode_params* params,
+                             const ldpc_channel_params* channel, const ldpc_es_word_outputs* outputs,
+                             void* stream);
+/* Whether ldpc_decode_es_word serves these parameters on this context: 1, 0, or a negative
+   status. */
+int ldpc_es_word_supported(const ldpc_ctx* ctx, const ldpc_decode_params* params);
+
 /* The LLR rows ldpc_channel_awgn(B, ..., offset) would write at batch rows idx_dev[0..n) (each
    index < B, any order), into rows_dev[n][n_vars]: the same values bit for bit, generated for
    those codewords only -- the uncorrected-word sweep regenerates the few failing frames' rows

@@ -758,7 +758,8 @@ bool bs_q8_ok(const DevGraph& g, int mode, bool ucn, float clip, int T, bool has
 }
 
 // one launch of plan p; es: the early-stop outputs (an ES instance's plan), else null
-struct EsOut { uint8_t* n_iter; int64_t* iter_hist; };
+// (hdw: the plane buffer of the stop-iteration words, or null: DESIGN 3.9)
+struct EsOut { uint8_t* n_iter; int64_t* iter_hist; uint32_t* hdw; };
 static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const BsPlan& p, const float* llr, int mode,
                   bool ucn, int64_t* counters, uint8_t* flags, uint32_t* bad, uint32_t* hdx, bool word,
                   const EsOut* es, hipStream_t s) {
@@ -776,10 +777,11 @@ static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const Bs
     const uint32_t* gt = reinterpret_cast<const uint32_t*>(es ? ws.bs_es_graph : ws.bs_graph);
     // (BsArgs, and the early-stop builds' additions: an ES instance's launch reads them, every
     // other launch takes the BsArgs base alone)
-    BsArgsEs a{};
+    BsArgsEw a{};
     if (es) {
         a.n_iter = es->n_iter;
         a.iter_hist = es->iter_hist;
+        a.hdw = es->hdw;
     }
     a.llr = llr;
     if (b.q8) {                          // the in-prologue channel (ldpc_decode_awgn)
@@ -930,10 +932,12 @@ const char* bs_es_kernel_name(const DevGraph& g, int mode, bool ucn, bool per_ed
 // the early-stop decode of b.B codewords (LLRs at llr, or the in-prologue channel b.q8 / b.gen8):
 // counters [0..2], frame flags, n_iter [B] and iter_hist [T], each or null.  Packs with an LLR off
 // the grid are marked (flags 0x80, n_iter 0), not decoded.  LDPC_ERR_UNSUPPORTED: no ES instance
-// serves the request; nothing was launched.
+// serves the request; nothing was launched.  hdw: null, or [packs][n_vars] u32 that takes each
+// codeword's hard decisions at its stop iteration (the EW builds; ws.bs_bad then holds the packs'
+// off-grid marks for word_out).
 int bs_decode_es(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode, bool ucn,
                  int ntiles_max, int64_t* counters, uint8_t* flags, uint8_t* n_iter, int64_t* iter_hist,
-                 hipStream_t s) {
+                 uint32_t* hdw, hipStream_t s) {
     const BsPlan p = bs_plan(g, mode, ucn, false, b.clip, b.T, true);
     // (no bsl plan at all: the compressed kernel's early-stop builds, as bs_decode's fall-through)
     const bool to_bsc = !p.ok && es_falls_to_bsc(g, mode, ucn, false, b.clip, b.T) &&
@@ -953,8 +957,8 @@ int bs_decode_es(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const flo
         }
         ws.bs_bad_n = n;
     }
-    if (to_bsc) return bsc_decode_es(g, b, ws, llr, mode, ucn, counters, flags, ws.bs_bad, n_iter, iter_hist, s);
-    const EsOut es{n_iter, iter_hist};
+    if (to_bsc) return bsc_decode_es(g, b, ws, llr, mode, ucn, counters, flags, ws.bs_bad, n_iter, iter_hist, hdw, s);
+    const EsOut es{n_iter, iter_hist, hdw};
     return bs_run(g, b, ws, p, llr, mode, ucn, counters, flags, ws.bs_bad, nullptr, false, &es, s);
 }
 

@@ -147,6 +147,13 @@ struct BsArgsEs : BsArgs {
     // word t = OR over the checks of the syndrome of iteration t's hard decisions)
 };
 
+// The arguments of the early-stop builds that keep the decoded word (EW): BsArgsEs and
+// the plane buffer, so the ES builds' kernel arguments stay as they are.
+struct BsArgsEw : BsArgsEs {
+    uint32_t* hdw;               // [packs][n_vars] each codeword's hard decisions at its stop
+                                 // iteration (bit r = codeword 32 pack + r), or null: off
+};
+
 // The export builds' arguments (XP): BsArgs and the word mode's switch, carried the
 // same way.
 struct BsArgsXp : BsArgs {
@@ -626,17 +633,20 @@ constexpr bool bs_loops(const BsInst& k) { return k.VPL == 1 && k.CPL == 1 && !k
 // Q8: the channel generated in the prologue (a.gen: ldpc_decode_awgn) instead of read as float
 // LLRs; a build of its own (a run-time branch moved the register allocation of the whole kernel: C3's
 // spills 5 -> 9 VGPRs)
+// EW: the early-stop build that also keeps each codeword's hard decisions at its stop iteration
+// (DESIGN 3.9): a build of its own beside the ES build, which stays as it is.
 // ES: the early-stop build (one-chunk UCN-compiled instances, one pack per
 // workgroup).  The hard decisions go to HD and the check phases take their syndromes at every
 // iteration; a pack leaves the T loop once each of its codewords has had a zero syndrome, and the
 // epilogue takes every codeword's outputs at its own first zero-syndrome iteration.
 template <int D, int DV, int LPC, int VPL, int CPL, bool UCN, bool BIG, bool PK, int WPE, bool XP, int LB, bool Q8,
-          bool ES = false>
+          bool ES = false, bool EW = false>
 __global__ void __launch_bounds__(LB) __attribute__((amdgpu_waves_per_eu(WPE)))
-k_bs(std::conditional_t<ES, BsArgsEs, std::conditional_t<XP, BsArgsXp, BsArgs>> a) {
+k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::conditional_t<XP, BsArgsXp, BsArgs>> a) {
     static_assert(LPC == 2 || LPC == 4, "lanes per check");
-    using KArgs = std::conditional_t<ES, BsArgsEs, std::conditional_t<XP, BsArgsXp, BsArgs>>;
+    using KArgs = std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::conditional_t<XP, BsArgsXp, BsArgs>>;
     static_assert(!ES || (UCN && VPL == 1 && CPL == 1 && !XP), "early stop: one-chunk UCN-compiled instances");
+    static_assert(!EW || ES, "the stop-iteration word: early-stop builds");
     constexpr int SB = (DV * QMAX + QMAX <= 127) ? 8 : 9;     // planes of S and of lw + S
     constexpr int EPL = (D + LPC - 1) / LPC;                     // edge slots per check lane
     constexpr bool SKIPM = CPL > 1;                              // chunk-wide padding skipped
@@ -798,6 +808,9 @@ k_bs(std::conditional_t<ES, BsArgsEs, std::conditional_t<XP, BsArgsXp, BsArgs>> 
     if constexpr (ES) {
         for (int w = tid; w < a.T; w += NT) RED[flor + FLORW + w] = 0u;
     }
+    // (EW: the lane's variable's hard decisions, each codeword's bit taken at its stop iteration;
+    // one register through the loop, stored once after it)
+    [[maybe_unused]] uint32_t es_hd = 0u;
     // (the barrier that orders these writes before the channel's flag updates: here when the
     // channel is generated from the sampler's tables; else after the first variable's LLR loads
     // are issued, so that it waits beside their HBM round trip, EBR)
@@ -1094,6 +1107,10 @@ k_bs(std::conditional_t<ES, BsArgsEs, std::conditional_t<XP, BsArgsXp, BsArgs>> 
                             else
                             nb += (uint32_t)__popc(hd);
                         }
+                    }
+                    // (the codewords that never stopped keep iteration T - 1's decisions)
+                    if constexpr (EW) {
+                        if (last) es_hd |= hd & ~es_done;
                     }
                 }
                 if (last) return;
@@ -1533,6 +1550,14 @@ k_bs(std::conditional_t<ES, BsArgsEs, std::conditional_t<XP, BsArgsXp, BsArgs>> 
                 if (nn) {
                     const int v = vv[0] >= 0 ? (vv[0] & 0xFFFF) : -1;
                     uint32_t nb = 0u;
+                    if constexpr (EW) {
+                        // (every real variable's decisions, not the target bits' alone)
+                        if (v >= 0) {
+                            const uint32_t h = lds_w(4u * ((uint32_t)vv[0] >> 16)) & nn;
+                            es_hd |= h;
+                            if (v < a.target_bits) nb = (uint32_t)__popc(h);
+                        }
+                    } else
                     if (v >= 0 && v < a.target_bits)
                         nb = (uint32_t)__popc(lds_w(4u * ((uint32_t)vv[0] >> 16)) & nn);
                     nb = wave_add(nb);
@@ -1575,6 +1600,13 @@ k_bs(std::conditional_t<ES, BsArgsEs, std::conditional_t<XP, BsArgsXp, BsArgs>> 
 #else
     const int te = tid;
 #endif
+    if constexpr (EW) {
+        // the pack's row of the stop-iteration hard decisions: every word from the lane that owns
+        // the variable, one store (a pack off the grid never gets here: word_out zeroes its rows)
+        uint32_t* hdw = kern_args<KArgs>().hdw;
+        const int v = vv[0] >= 0 ? (vv[0] & 0xFFFF) : -1;
+        if (hdw && v >= 0) hdw[(size_t)BS_PK * nv + v] = es_hd;
+    }
     if constexpr (ES) {
         // early stop: each codeword's outputs at its own stop iteration -- the first t whose
         // syndrome word has its bit clear, else T - 1 -- from the syndrome words and the
@@ -1737,11 +1769,11 @@ int launch_bs(const BsArgs& a, int npacks, int nw, size_t lds, hipStream_t s, bo
 
 // the early-stop builds of an ES instance (float LLRs, or the in-prologue channel): one workgroup
 // per pack, no pack loop (packs end at different times) and no export build
-template <int I, bool Q8>
-int launch_bs_es_x(const BsArgsEs& a, int npacks, int nw, size_t lds, hipStream_t s) {
+template <int I, bool Q8, bool EW>
+int launch_bs_es_x(const std::conditional_t<EW, BsArgsEw, BsArgsEs>& a, int npacks, int nw, size_t lds, hipStream_t s) {
     constexpr BsInst k = kBsInst[I];
     static_assert(k.ES && !bs_loops(k), "an early-stop instance");
-    auto* fn = &k_bs<k.D, k.DV, k.LPC, k.VPL, k.CPL, k.UCN, k.BIG, k.PK, k.WPE, false, 1024, Q8, true>;
+    auto* fn = &k_bs<k.D, k.DV, k.LPC, k.VPL, k.CPL, k.UCN, k.BIG, k.PK, k.WPE, false, 1024, Q8, true, EW>;
     static bool attr = false;
     if (!attr) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
@@ -1751,14 +1783,20 @@ int launch_bs_es_x(const BsArgsEs& a, int npacks, int nw, size_t lds, hipStream_
     hipLaunchKernelGGL(fn, dim3(npacks), dim3(64 * nw), lds, s, a);
     return hipGetLastError() == hipSuccess ? LDPC_OK : LDPC_ERR_HIP;
 }
-// instance I's launch: an ES instance is handed the early-stop arguments (BsArgsEs, passed as
+// instance I's launch: an ES instance is handed the early-stop arguments (BsArgsEw, passed as
 // their BsArgs base) and has no other build; the others never see them
 template <int I>
 int launch_bs_any(const BsArgs& a, int npacks, int nw, size_t lds, hipStream_t s, bool q8, int grid, int* resident) {
     if constexpr (kBsInst[I].ES) {
         if (a.hdx) return LDPC_ERR_UNSUPPORTED;
-        const BsArgsEs& ae = static_cast<const BsArgsEs&>(a);
-        return q8 ? launch_bs_es_x<I, true>(ae, npacks, nw, lds, s) : launch_bs_es_x<I, false>(ae, npacks, nw, lds, s);
+        const BsArgsEw& aw = static_cast<const BsArgsEw&>(a);
+        // (with a plane buffer for the stop-iteration words, the EW build: DESIGN 3.9)
+        if (aw.hdw)
+            return q8 ? launch_bs_es_x<I, true, true>(aw, npacks, nw, lds, s)
+                      : launch_bs_es_x<I, false, true>(aw, npacks, nw, lds, s);
+        const BsArgsEs& ae = aw;
+        return q8 ? launch_bs_es_x<I, true, false>(ae, npacks, nw, lds, s)
+                  : launch_bs_es_x<I, false, false>(ae, npacks, nw, lds, s);
     } else {
         return launch_bs<I>(a, npacks, nw, lds, s, q8, grid, resident);
     }

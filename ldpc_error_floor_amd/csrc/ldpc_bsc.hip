@@ -90,6 +90,13 @@ struct BscArgsEs : BscArgs {
                                  // = OR over the checks of the syndrome of iteration t's hard decisions
 };
 
+// The arguments of the early-stop builds that keep the decoded word (EW; as bsl's
+// BsArgsEw): the ES builds' kernel arguments stay as they are.
+struct BscArgsEw : BscArgsEs {
+    uint32_t* hdw;               // [packs][n_vars] each codeword's hard decisions at its stop
+                                 // iteration, or null: off
+};
+
 typedef unsigned int v2u __attribute__((ext_vector_type(2)));
 
 // Check records in blocks of 16: the q1 words of records 16 b .. 16 b + 15 (256 B), then their q2
@@ -114,11 +121,18 @@ __device__ __forceinline__ void lds_dput(uint32_t addr, uint32_t x, uint32_t y) 
 // stores is clamp6(Q(ch) + S), whose sign is the sign of APP_t bit for bit (the same planes into
 // the same adder), so iteration t's hard decisions are ~TV[v] plane 5 and need no table of their
 // own: check phase t + 1 XORs them over each check's real edges into syndrome word U[t].
+// EW: the early-stop build that also keeps each codeword's hard decisions at its stop iteration
+// (DESIGN 3.9), a build of its own beside the ES build.  A lane holds up to VPL variables and the
+// C5 build has no register to carry a word for each through the loop, so the lane that owns a
+// variable ORs into the pack's row in global memory: zero at the start, hd_t & nn on the few
+// iterations where codewords stop, hd_{T-1} & ~done in the last variable phase.  The ORs are
+// atomics without a return value, so no wave waits for memory inside the loop.
 template <int D, int DVH, int DVL, int LPC, int VPL, int CPL, int WPE, bool XP, int LB, bool MIX, bool B1, bool Q8,
-          bool ES = false>
+          bool ES = false, bool EW = false>
 __global__ void __launch_bounds__(LB) __attribute__((amdgpu_waves_per_eu(WPE)))
-k_bsc(std::conditional_t<ES, BscArgsEs, std::conditional_t<XP, BscArgsXp, BscArgs>> a) {
+k_bsc(std::conditional_t<ES, std::conditional_t<EW, BscArgsEw, BscArgsEs>, std::conditional_t<XP, BscArgsXp, BscArgs>> a) {
     static_assert(!ES || (B1 && !XP), "early stop: the beta = 1 build, no export");
+    static_assert(!EW || ES, "the stop-iteration word: early-stop builds");
     constexpr int SB = (DVH * QMAX + QMAX <= 127) ? 8 : 9;
     constexpr int EPL = (D + LPC - 1) / LPC;
     constexpr int VNW = DVH + 1;
@@ -214,6 +228,21 @@ k_bsc(std::conditional_t<ES, BscArgsEs, std::conditional_t<XP, BscArgsXp, BscArg
         return;
     }
     if (tid == 0) a.bad[blockIdx.x] = 0u;
+    // (EW: the pack's row of stop-iteration hard decisions starts from zero; the barriers before
+    // the loop retire these stores)
+    // (the row's address is taken from the kernel arguments at each use, scalar loads, not held
+    // through the loop)
+    [[maybe_unused]] auto hdw_row = [&]() __attribute__((always_inline)) -> uint32_t* {
+        uint32_t* h = kern_args<BscArgsEw>().hdw;
+        return h ? h + (size_t)blockIdx.x * (size_t)kern_args<BscArgsEw>().n_vars : nullptr;
+    };
+    if constexpr (EW) {
+        if (uint32_t* row = hdw_row()) {
+#pragma unroll
+            for (int u = 0; u < VPL; ++u)
+                if (vv[u] >= 0) row[vv[u] & 0xFFFF] = 0u;
+        }
+    }
     // the zero edge / zero record (padding edges of the variable lanes), counters, tables
     if (tid < 8)
         reinterpret_cast<uint32_t*>(smem + a.off_rec + rec_off((uint32_t)a.n_checks) + (tid >> 2) * REC_Q2)[tid & 3] = 0u;
@@ -268,6 +297,7 @@ k_bsc(std::conditional_t<ES, BscArgsEs, std::conditional_t<XP, BscArgsXp, BscArg
                 }
             }
             const int dwu = dw[u];
+            [[maybe_unused]] uint32_t hl = 0u;    // (EW: the variable's hard decisions, for the merge below)
             // the rest at SBX planes of S: the fewest that hold 15 dw + 15 for the place's largest
             // degree (as bsl; the places past the first hold at most DVL edges)
             auto vbody = [&](auto sbc) __attribute__((always_inline)) {
@@ -325,6 +355,7 @@ k_bsc(std::conditional_t<ES, BscArgsEs, std::conditional_t<XP, BscArgsXp, BscArg
                             else nb += (uint32_t)__popc(hd);
                         }
                     }
+                    if constexpr (EW) hl = hd;
                 }
                 if (last || v < 0) return;
                 uint32_t lb[4];
@@ -348,6 +379,13 @@ k_bsc(std::conditional_t<ES, BscArgsEs, std::conditional_t<XP, BscArgsXp, BscArg
             constexpr int SBL = (DVL * QMAX + QMAX <= 127) ? 8 : 9;    // places past the first
             if (u == 0) dispatch(std::integral_constant<int, SB>{});
             else dispatch(std::integral_constant<int, SBL>{});
+            // (EW: the codewords that never stopped keep iteration T - 1's decisions)
+            if constexpr (EW) {
+                if (last && v >= 0 && (hl & ~es_done)) {
+                    if (uint32_t* row = hdw_row())
+                        __hip_atomic_fetch_or(row + v, hl & ~es_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
         }
         if (!first && !last) {               // (as bsl: one ds_or per lane into the FLORW words)
             const uint32_t la = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) & 31u;
@@ -607,6 +645,17 @@ k_bsc(std::conditional_t<ES, BscArgsEs, std::conditional_t<XP, BscArgsXp, BscArg
 #pragma unroll
                     for (int u = 0; u < VPL; ++u) {
                         const int v = vv[u] < 0 ? -1 : (vv[u] & 0xFFFF);
+                        if constexpr (EW) {
+                            // (every real variable's decisions, not the target bits' alone)
+                            if (v >= 0) {
+                                const uint32_t h = ~lds_w(a.off_tv + 24u * ((uint32_t)vv[u] >> 16) + 20u) & nn;
+                                if (h) {
+                                    if (uint32_t* row = hdw_row())
+                                        __hip_atomic_fetch_or(row + v, h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                }
+                                if (v < a.target_bits) nb += (uint32_t)__popc(h);
+                            }
+                        } else
                         if (v >= 0 && v < a.target_bits)
                             nb += (uint32_t)__popc(~lds_w(a.off_tv + 24u * ((uint32_t)vv[u] >> 16) + 20u) & nn);
                     }
@@ -1026,11 +1075,11 @@ static int bsc_launch(const BscArgs& a, int nblocks, int nw, size_t lds, hipStre
 }
 // the early-stop builds of instance I (float LLRs, or the in-prologue channel): the B1 build, one
 // workgroup per pack, no export build
-template <int I, bool Q8>
-static int bsc_launch_es(const BscArgsEs& a, int nblocks, int nw, size_t lds, hipStream_t s) {
+template <int I, bool Q8, bool EW>
+static int bsc_launch_es1(const std::conditional_t<EW, BscArgsEw, BscArgsEs>& a, int nblocks, int nw, size_t lds, hipStream_t s) {
     constexpr BscInst k = kBscInst[I];
     static_assert(bsc_es_inst(I) && k.MIX, "an early-stop instance");
-    auto* fn = &k_bsc<k.D, k.DVH, k.DVL, k.LPC, k.VPL, k.CPL, k.WPE, false, 64 * k.NW, k.MIX, true, Q8, true>;
+    auto* fn = &k_bsc<k.D, k.DVH, k.DVL, k.LPC, k.VPL, k.CPL, k.WPE, false, 64 * k.NW, k.MIX, true, Q8, true, EW>;
     static bool attr = false;
     if (!attr) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
@@ -1039,6 +1088,11 @@ static int bsc_launch_es(const BscArgsEs& a, int nblocks, int nw, size_t lds, hi
     }
     hipLaunchKernelGGL(fn, dim3(nblocks), dim3(64 * nw), lds, s, a);
     return hipGetLastError() == hipSuccess ? LDPC_OK : LDPC_ERR_HIP;
+}
+// (with a plane buffer for the stop-iteration words, the EW build: DESIGN 3.9)
+template <int I, bool Q8>
+static int bsc_launch_es(const BscArgsEw& a, int nblocks, int nw, size_t lds, hipStream_t s) {
+    return a.hdw ? bsc_launch_es1<I, Q8, true>(a, nblocks, nw, lds, s) : bsc_launch_es1<I, Q8, false>(a, nblocks, nw, lds, s);
 }
 
 }  // namespace bs
@@ -1148,7 +1202,7 @@ const char* bsc_es_kernel_name(const DevGraph& g, int mode, bool ucn, bool per_e
 }
 
 // one launch of plan p; es: the early-stop outputs (an early-stop plan), else null
-struct BscEsOut { uint8_t* n_iter; int64_t* iter_hist; };
+struct BscEsOut { uint8_t* n_iter; int64_t* iter_hist; uint32_t* hdw; };
 static int bsc_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const BscPlan& p, const float* llr, int mode,
                    int64_t* counters, uint8_t* flags, uint32_t* bad, uint32_t* hdx, bool word, const BscEsOut* es,
                    hipStream_t s) {
@@ -1164,11 +1218,12 @@ static int bsc_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const B
     const int VNW = k.DVH + 1;
     // (BscArgs, and the early-stop builds' additions: their launch reads them, every other launch
     // takes the BscArgs base alone)
-    BscArgsEs a{};
+    BscArgsEw a{};
     if (es) {
         a.n_iter = es->n_iter;
         a.iter_hist = es->iter_hist;
         a.off_u = p.off_u;
+        a.hdw = es->hdw;
     }
     const bool q8 = b.q8 != nullptr;
     a.llr = llr;
@@ -1258,12 +1313,12 @@ int bsc_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float
 // nothing launched when no early-stop build serves the request
 int bsc_decode_es(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode, bool ucn,
                   int64_t* counters, uint8_t* flags, uint32_t* bad, uint8_t* n_iter, int64_t* iter_hist,
-                  hipStream_t s) {
+                  uint32_t* hdw, hipStream_t s) {
     const BscPlan p = bsc_plan(g, mode, ucn, false, b.clip, b.T, true);
     if (!p.ok) return LDPC_ERR_UNSUPPORTED;
     if (b.q8 && !bsc_es_q8_ok(g, mode, ucn, b.clip, b.T, reinterpret_cast<const AwgnParams*>(b.gen8)->ss > 0))
         return LDPC_ERR_UNSUPPORTED;
-    const BscEsOut es{n_iter, iter_hist};
+    const BscEsOut es{n_iter, iter_hist, hdw};
     return bsc_run(g, b, ws, p, llr, mode, counters, flags, bad, nullptr, false, &es, s);
 }
 

@@ -735,8 +735,23 @@ int ldpc_es_supported(const ldpc_ctx* c, const ldpc_decode_params* p) {
     return st == LDPC_OK ? 1 : st == LDPC_ERR_UNSUPPORTED ? 0 : st;
 }
 
+// (what either early-stop entry point asks for; hard_stop: the decoded word too)
+struct EsOuts {
+    int64_t* counters;
+    uint8_t *frame_flags, *n_iter;
+    int64_t* iter_hist;
+    uint32_t* hard_stop;
+    uint8_t* word_flags;
+};
+static EsOuts es_outs(const ldpc_es_outputs* o) {
+    return EsOuts{o->counters, o->frame_flags, o->n_iter, o->iter_hist, nullptr, nullptr};
+}
+static EsOuts es_outs(const ldpc_es_word_outputs* o) {
+    return EsOuts{o->counters, o->frame_flags, o->n_iter, o->iter_hist, o->hard_stop, o->word_flags};
+}
+
 static int decode_es_impl(ldpc_ctx* c, const float* llr_dev, int64_t B, const ldpc_decode_params* p,
-                          const ldpc_es_outputs* o, void* stream, const uint32_t* q8, const AwgnParams* gen8) {
+                          const EsOuts& o, void* stream, const uint32_t* q8, const AwgnParams* gen8) {
     int mode = -1;
     const int rq = es_request(c, B, p, &mode);
     if (rq != LDPC_OK) return rq;
@@ -757,25 +772,31 @@ static int decode_es_impl(ldpc_ctx* c, const float* llr_dev, int64_t B, const ld
     b.count = 1;
     b.q8 = q8;
     b.gen8 = gen8;
-    const int st = bs_decode_es(g->dev, b, c->fused, llr_dev, mode, ucn, c->ntiles_max, o->counters,
-                                o->frame_flags, o->n_iter, o->iter_hist, s);
+    const int st = o.hard_stop
+        ? fused_decode_es_word(g->dev, b, c->fused, llr_dev, mode, ucn, c->B_max, c->ntiles_max, o.counters,
+                               o.frame_flags, o.n_iter, o.iter_hist, o.hard_stop, o.word_flags, s)
+        : bs_decode_es(g->dev, b, c->fused, llr_dev, mode, ucn, c->ntiles_max, o.counters, o.frame_flags,
+                       o.n_iter, o.iter_hist, nullptr, s);
     if (st != LDPC_OK) return st;
-    std::snprintf(c->last_kernel, sizeof(c->last_kernel), "%s%s",
-                  bs_es_kernel_name(g->dev, mode, ucn, false, p->clip_llr, p->T), q8 ? "+gen" : "");
+    const char* nm = bs_es_kernel_name(g->dev, mode, ucn, false, p->clip_llr, p->T);
+    if (o.hard_stop) {                   // the early-stop name with ",word" inside the brackets
+        const size_t n = std::strlen(nm);
+        std::snprintf(c->last_kernel, sizeof(c->last_kernel), "%.*s,word]%s", (int)(n ? n - 1 : 0), nm,
+                      q8 ? "+gen" : "");
+    } else {
+        std::snprintf(c->last_kernel, sizeof(c->last_kernel), "%s%s", nm, q8 ? "+gen" : "");
+    }
     return hipGetLastError() == hipSuccess ? LDPC_OK : LDPC_ERR_HIP;
 }
 
 int ldpc_decode_es(ldpc_ctx* c, const float* llr_dev, int64_t B, const ldpc_decode_params* p,
                    const ldpc_es_outputs* o, void* stream) {
     if (!c || !llr_dev || !p || !o || o->size != (int32_t)sizeof(ldpc_es_outputs)) return LDPC_ERR_ARG;
-    return decode_es_impl(c, llr_dev, B, p, o, stream, nullptr, nullptr);
+    return decode_es_impl(c, llr_dev, B, p, es_outs(o), stream, nullptr, nullptr);
 }
 
-int ldpc_decode_awgn_es(ldpc_ctx* c, int64_t B, const ldpc_decode_params* p, const ldpc_channel_params* ch,
-                        const ldpc_es_outputs* o, void* stream) {
-    if (!c || !p || !ch || !o || o->size != (int32_t)sizeof(ldpc_es_outputs) || !(ch->sigma > 0.0) ||
-        ch->offset < 0)
-        return LDPC_ERR_ARG;
+static int decode_awgn_es_impl(ldpc_ctx* c, int64_t B, const ldpc_decode_params* p, const ldpc_channel_params* ch,
+                               const EsOuts& o, void* stream) {
     int mode = -1;
     int st = es_request(c, B, p, &mode);
     if (st != LDPC_OK) return st;
@@ -809,6 +830,33 @@ int ldpc_decode_awgn_es(ldpc_ctx* c, int64_t B, const ldpc_decode_params* p, con
     if (st != LDPC_OK) return st;
     return decode_es_impl(c, c->llr_scratch, B, p, o, stream, nullptr, nullptr);
 }
+
+int ldpc_decode_awgn_es(ldpc_ctx* c, int64_t B, const ldpc_decode_params* p, const ldpc_channel_params* ch,
+                        const ldpc_es_outputs* o, void* stream) {
+    if (!c || !p || !ch || !o || o->size != (int32_t)sizeof(ldpc_es_outputs) || !(ch->sigma > 0.0) ||
+        ch->offset < 0)
+        return LDPC_ERR_ARG;
+    return decode_awgn_es_impl(c, B, p, ch, es_outs(o), stream);
+}
+
+// ---- early stop with the decoded word (include/ldpc_nms.h) ----------------------
+// (the outputs' size and the required row pointer are checked before the context is read)
+static_assert(sizeof(ldpc_es_word_outputs) == 64, "ldpc_es_word_outputs is part of ABI 3");
+int ldpc_decode_es_word(ldpc_ctx* c, const float* llr_dev, int64_t B, const ldpc_decode_params* p,
+                        const ldpc_es_word_outputs* o, void* stream) {
+    if (!o || o->size != (int32_t)sizeof(ldpc_es_word_outputs) || !o->hard_stop) return LDPC_ERR_ARG;
+    if (!c || !llr_dev || !p) return LDPC_ERR_ARG;
+    return decode_es_impl(c, llr_dev, B, p, es_outs(o), stream, nullptr, nullptr);
+}
+
+int ldpc_decode_awgn_es_word(ldpc_ctx* c, int64_t B, const ldpc_decode_params* p, const ldpc_channel_params* ch,
+                             const ldpc_es_word_outputs* o, void* stream) {
+    if (!o || o->size != (int32_t)sizeof(ldpc_es_word_outputs) || !o->hard_stop) return LDPC_ERR_ARG;
+    if (!c || !p || !ch || !(ch->sigma > 0.0) || ch->offset < 0) return LDPC_ERR_ARG;
+    return decode_awgn_es_impl(c, B, p, ch, es_outs(o), stream);
+}
+
+int ldpc_es_word_supported(const ldpc_ctx* c, const ldpc_decode_params* p) { return ldpc_es_supported(c, p); }
 
 // ---- decoded word (include/ldpc_nms.h) ------------------------------------------
 // the request's mode when the bit-sliced kernels decode it, LDPC_ERR_UNSUPPORTED when they do

@@ -24,8 +24,9 @@ struct FusedWorkspace {
     uint32_t* hdx = nullptr;       // [T][packs][n_vars] bit-sliced hard decisions (bit export of
     int64_t hdx_elems = 0;         // the bit-sliced kernels; fixup packs are in `hd` instead)
     bool bits_packed = false;      // the last bit-exporting decode wrote hdx (+ hd for bad packs)
-    uint32_t* hdw = nullptr;       // [ceil(B_max / 32)][n_vars] the word mode's last-iteration hard
-    int64_t hdw_elems = 0;         // decisions, bit-sliced (allocated on first use)
+    uint32_t* hdw = nullptr;       // [ceil(B_max / 32)][n_vars] the word modes' hard decisions (last
+    int64_t hdw_elems = 0;         // iteration's; stop iteration's, 3.9), bit-sliced;
+                                   // allocated on first use
     const char* last_kernel = "";  // the kernel that served the last decode (ldpc_ctx_last_kernel)
     // what the per-decode table kernels last wrote (they depend only on the graph, the weights
     // and T): a decode with the same key skips them
@@ -83,13 +84,15 @@ int bsc_debug_bounds(const DevGraph& g, int mode, float clip, int T, int flags, 
 // early stop (ldpc_decode_es): the bit-sliced kernel's ES instances serve the request,
 // or, for a graph that no bsl plan serves, the compressed kernel's early-stop builds (bsc_*_es);
 // their decode (counters [0..2], frame flags, n_iter [B], iter_hist [T], each or null; b.q8 / gen8:
-// the in-prologue channel, when bs_es_q8_ok) and its kernel name ("bsl[...,es]" / "bsc[...,es]")
+// the in-prologue channel, when bs_es_q8_ok) and its kernel name ("bsl[...,es]" / "bsc[...,es]").
+// hdw: null, or [packs][n_vars] u32 that takes each codeword's hard decisions at its stop
+// iteration (the EW builds)
 bool bs_es_supported(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T);
 bool bs_es_q8_ok(const DevGraph& g, int mode, bool ucn, float clip, int T, bool has_short);
 const char* bs_es_kernel_name(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T);
 int bs_decode_es(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode, bool ucn,
                  int ntiles_max, int64_t* counters, uint8_t* flags, uint8_t* n_iter, int64_t* iter_hist,
-                 hipStream_t s);
+                 uint32_t* hdw, hipStream_t s);
 // (fused_decode with it: the bit-sliced kernel or LDPC_ERR_UNSUPPORTED)
 bool fused_q8_ok(const DevGraph& g, int mode, int T, float clip, bool ucn, bool per_edge_w, bool has_short);
 // a decode with an in-kernel generator (Bufs::awgn) runs the v5 kernel's prologue channel
@@ -107,7 +110,7 @@ bool bsc_es_q8_ok(const DevGraph& g, int mode, bool ucn, float clip, int T, bool
 const char* bsc_es_kernel_name(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T);
 int bsc_decode_es(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode, bool ucn,
                   int64_t* counters, uint8_t* flags, uint32_t* bad, uint8_t* n_iter, int64_t* iter_hist,
-                  hipStream_t s);
+                  uint32_t* hdw, hipStream_t s);
 // the word mode (ldpc_decode_word): the request is one the bit-sliced kernels decode
 // (fused_decode would take bs_decode for its counters); the decode -- the export build storing
 // the last iteration's hard decisions alone into ws.hdw, no v5 fixup, then word_out --; and the
@@ -119,6 +122,13 @@ bool fused_word_supported(const DevGraph& g, int mode, int T, float clip, bool u
 int fused_decode_word(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode, bool ucn,
                       int64_t B_max, int64_t* counters, uint8_t* flags, uint32_t* hard_last,
                       uint8_t* word_flags, hipStream_t s);
+// the early-stop decode with the decoded word (ldpc_decode_es_word): bs_decode_es with
+// ws.hdw (sized as fused_decode_word's) taking each codeword's hard decisions at its stop
+// iteration, then word_out: hard_stop [B][ceil(n_vars / 32)], word_flags [B] or null.  Served
+// exactly where bs_decode_es is.
+int fused_decode_es_word(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode, bool ucn,
+                         int64_t B_max, int ntiles_max, int64_t* counters, uint8_t* flags, uint8_t* n_iter,
+                         int64_t* iter_hist, uint32_t* hard_stop, uint8_t* word_flags, hipStream_t s);
 int word_out(const DevGraph& g, const uint32_t* planes, const uint32_t* bad, int64_t B, uint32_t* hard_last,
              uint8_t* word_flags, uint8_t* frame_flags, hipStream_t s);
 void fused_free(FusedWorkspace& ws);

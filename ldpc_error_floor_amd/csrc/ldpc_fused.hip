@@ -12,6 +12,7 @@
 #include <cstdlib>
 
 #include "ldpc_fused.h"
+#include "ldpc_awgn.h"
 
 namespace ldpc {
 
@@ -167,12 +168,9 @@ bool fused_word_supported(const DevGraph& g, int mode, int T, float clip, bool u
     return fused_supported(g, mode, T, clip) && g.n_vars <= WORD_MAX_VARS && use_bs(g, mode, T, ucn, per_edge_w, clip);
 }
 
-int fused_decode_word(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode, bool ucn,
-                      int64_t B_max, int64_t* counters, uint8_t* flags, uint32_t* hard_last,
-                      uint8_t* word_flags, hipStream_t s) {
-    if (!fused_word_supported(g, mode, b.T, b.clip, ucn, false)) return LDPC_ERR_UNSUPPORTED;
-    // the scratch: one word per (pack, variable) of the largest batch, whatever T is
-    const int64_t npk_max = (B_max + 31) / 32, n = npk_max * g.n_vars;
+// the word modes' scratch: one word per (pack, variable) of the largest batch, whatever T is
+static int word_scratch(const DevGraph& g, FusedWorkspace& ws, int64_t B_max) {
+    const int64_t n = ((B_max + 31) / 32) * g.n_vars;
     if (n > ws.hdw_elems) {
         if (ws.hdw) (void)hipFree(ws.hdw);
         ws.hdw = nullptr;
@@ -183,6 +181,16 @@ int fused_decode_word(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, cons
         }
         ws.hdw_elems = n;
     }
+    return LDPC_OK;
+}
+
+int fused_decode_word(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode, bool ucn,
+                      int64_t B_max, int64_t* counters, uint8_t* flags, uint32_t* hard_last,
+                      uint8_t* word_flags, hipStream_t s) {
+    if (!fused_word_supported(g, mode, b.T, b.clip, ucn, false)) return LDPC_ERR_UNSUPPORTED;
+    const int64_t npk_max = (B_max + 31) / 32;
+    const int sw = word_scratch(g, ws, B_max);
+    if (sw != LDPC_OK) return sw;
     if (npk_max > ws.bs_bad_n) {         // (the kernel's per-pack off-grid word, as fused_decode's)
         if (ws.bs_bad) (void)hipFree(ws.bs_bad);
         ws.bs_bad = nullptr;
@@ -197,6 +205,23 @@ int fused_decode_word(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, cons
     const int st = bs_decode(g, b, ws, llr, mode, ucn, counters, flags, ws.bs_bad, ws.hdw, true, s);
     if (st != LDPC_OK) return st;
     return word_out(g, ws.hdw, ws.bs_bad, b.B, hard_last, word_flags, flags, s);
+}
+
+int fused_decode_es_word(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode, bool ucn,
+                         int64_t B_max, int ntiles_max, int64_t* counters, uint8_t* flags, uint8_t* n_iter,
+                         int64_t* iter_hist, uint32_t* hard_stop, uint8_t* word_flags, hipStream_t s) {
+    // (nothing allocated or launched for a request the early-stop builds do not serve; word_out's
+    // LDS holds the 4 variables on 1024 lanes that bound every bit-sliced plan)
+    if (!bs_es_supported(g, mode, ucn, false, b.clip, b.T) || g.n_vars > WORD_MAX_VARS || b.B > B_max)
+        return LDPC_ERR_UNSUPPORTED;
+    if (b.q8 && !bs_es_q8_ok(g, mode, ucn, b.clip, b.T, reinterpret_cast<const AwgnParams*>(b.gen8)->ss > 0))
+        return LDPC_ERR_UNSUPPORTED;
+    const int sw = word_scratch(g, ws, B_max);
+    if (sw != LDPC_OK) return sw;
+    // (bs_decode_es sizes ws.bs_bad; both kernels write every pack's off-grid mark into it)
+    const int st = bs_decode_es(g, b, ws, llr, mode, ucn, ntiles_max, counters, flags, n_iter, iter_hist, ws.hdw, s);
+    if (st != LDPC_OK) return st;
+    return word_out(g, ws.hdw, ws.bs_bad, b.B, hard_stop, word_flags, flags, s);
 }
 
 HdView fused_bits_view(const FusedWorkspace& ws) {

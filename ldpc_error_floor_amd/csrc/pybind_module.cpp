@@ -217,6 +217,80 @@ PYBIND11_MODULE(_ldpc_nms, m) {
         },
         py::arg("ctx"), py::arg("T"), py::arg("decoding_type"), py::arg("q_bit"),
         py::arg("target_bits"), py::arg("kernel"), py::arg("clip_llr") = 20.0f);
+    // early stop with the decoded word (ldpc_decode_es_word / ldpc_decode_awgn_es_word /
+    // ldpc_es_word_supported)
+    m.def(
+        "decode_es_word",
+        [](Ctx& c, uintptr_t llr, int64_t B, int T, int decoding_type, int q_bit, int target_bits,
+           float clip, int kernel, uintptr_t hard_stop, uintptr_t word_flags, uintptr_t counters,
+           uintptr_t flags, uintptr_t n_iter, uintptr_t iter_hist, uintptr_t stream) {
+            ldpc_decode_params p = make_params(T, decoding_type, q_bit, target_bits, clip, kernel);
+            ldpc_es_word_outputs o{};
+            o.size = (int32_t)sizeof(ldpc_es_word_outputs);
+            o.hard_stop = reinterpret_cast<uint32_t*>(hard_stop);
+            o.word_flags = reinterpret_cast<uint8_t*>(word_flags);
+            o.counters = reinterpret_cast<int64_t*>(counters);
+            o.frame_flags = reinterpret_cast<uint8_t*>(flags);
+            o.n_iter = reinterpret_cast<uint8_t*>(n_iter);
+            o.iter_hist = reinterpret_cast<int64_t*>(iter_hist);
+            int st;
+            {
+                py::gil_scoped_release nogil;
+                st = ldpc_decode_es_word(c.h, reinterpret_cast<const float*>(llr), B, &p, &o,
+                                         reinterpret_cast<void*>(stream));
+            }
+            check(st, "ldpc_decode_es_word");
+        },
+        py::arg("ctx"), py::arg("llr"), py::arg("B"), py::arg("T"), py::arg("decoding_type"),
+        py::arg("q_bit"), py::arg("target_bits"), py::arg("clip"), py::arg("kernel"),
+        py::arg("hard_stop"), py::arg("word_flags") = 0, py::arg("counters") = 0, py::arg("flags") = 0,
+        py::arg("n_iter") = 0, py::arg("iter_hist") = 0, py::arg("stream") = 0);
+    m.def(
+        "decode_awgn_es_word",
+        [](Ctx& c, int64_t B, int T, int decoding_type, int q_bit, int target_bits, float clip,
+           int kernel, double sigma, uint64_t seed, int64_t offset, int ps, int pe, int ss, int se,
+           uintptr_t hard_stop, uintptr_t word_flags, uintptr_t counters, uintptr_t flags,
+           uintptr_t n_iter, uintptr_t iter_hist, uintptr_t stream) {
+            ldpc_decode_params p = make_params(T, decoding_type, q_bit, target_bits, clip, kernel);
+            ldpc_channel_params ch{};
+            ch.sigma = sigma;
+            ch.seed = seed;
+            ch.offset = offset;
+            ch.punct_start = ps;
+            ch.punct_end = pe;
+            ch.short_start = ss;
+            ch.short_end = se;
+            ldpc_es_word_outputs o{};
+            o.size = (int32_t)sizeof(ldpc_es_word_outputs);
+            o.hard_stop = reinterpret_cast<uint32_t*>(hard_stop);
+            o.word_flags = reinterpret_cast<uint8_t*>(word_flags);
+            o.counters = reinterpret_cast<int64_t*>(counters);
+            o.frame_flags = reinterpret_cast<uint8_t*>(flags);
+            o.n_iter = reinterpret_cast<uint8_t*>(n_iter);
+            o.iter_hist = reinterpret_cast<int64_t*>(iter_hist);
+            int st;
+            {
+                py::gil_scoped_release nogil;
+                st = ldpc_decode_awgn_es_word(c.h, B, &p, &ch, &o, reinterpret_cast<void*>(stream));
+            }
+            check(st, "ldpc_decode_awgn_es_word");
+        },
+        py::arg("ctx"), py::arg("B"), py::arg("T"), py::arg("decoding_type"), py::arg("q_bit"),
+        py::arg("target_bits"), py::arg("clip"), py::arg("kernel"), py::arg("sigma"),
+        py::arg("seed"), py::arg("offset"), py::arg("punct_start"), py::arg("punct_end"),
+        py::arg("short_start"), py::arg("short_end"), py::arg("hard_stop"), py::arg("word_flags") = 0,
+        py::arg("counters") = 0, py::arg("flags") = 0, py::arg("n_iter") = 0, py::arg("iter_hist") = 0,
+        py::arg("stream") = 0);
+    m.def(
+        "es_word_supported",
+        [](Ctx& c, int T, int decoding_type, int q_bit, int target_bits, int kernel, float clip) {
+            ldpc_decode_params p = make_params(T, decoding_type, q_bit, target_bits, clip, kernel);
+            const int st = ldpc_es_word_supported(c.h, &p);
+            check(st, "ldpc_es_word_supported");
+            return st == 1;
+        },
+        py::arg("ctx"), py::arg("T"), py::arg("decoding_type"), py::arg("q_bit"),
+        py::arg("target_bits"), py::arg("kernel"), py::arg("clip_llr") = 20.0f);
     // decoded word (ldpc_decode_word / ldpc_word_supported)
     m.def(
         "decode_word",

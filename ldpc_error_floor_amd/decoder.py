@@ -37,7 +37,8 @@ class DecodeResult:
                                             # frame's pack held an off-grid LLR and was not decoded)
     iter_hist: Optional["object"] = None    # early stop: torch int64 [T], frames with n_iter == t+1
     hard_last: Optional["object"] = None    # word mode: torch int32 [B, ceil(N*z/32)], the last
-                                            # iteration's hard decisions (``unpack_bits`` unpacks them)
+                                            # iteration's hard decisions (``unpack_bits`` unpacks them);
+                                            # with early_stop, each frame's at its stop iteration
     word_flags: Optional["object"] = None   # word mode: torch uint8 [B], bit 0 = syndrome nonzero,
                                             # 0x80 = the frame's pack held an off-grid LLR (not decoded)
 
@@ -156,15 +157,20 @@ class NMSDecoder:
         return bool(self._ext.es_supported(ctx, T, self.decoding_type, self.q_bit, self.target_bits,
                                            KERNELS[kernel or self.kernel], self.clip))
 
-    def supports_hard_last(self, T=None, kernel=None) -> bool:
+    def supports_hard_last(self, T=None, kernel=None, early_stop: bool = False) -> bool:
         """Whether ``decode(..., hard_last=True)`` is served for this decoder
         (``ldpc_word_supported``): what the bit-sliced kernels decode -- a QMS grid with q in
         {5, -5, 4, 3}, no per-edge check weights, kernel auto or fused, and a graph the bit-sliced
-        kernel or the compressed one fits."""
+        kernel or the compressed one fits.  ``early_stop=True``: whether
+        ``decode(..., early_stop=True, hard_last=True)`` is (``ldpc_es_word_supported``): exactly
+        where ``supports_early_stop`` holds."""
         T = self.T if T is None else int(T)
         if T > self.T:
             return False
         ctx = self._ensure_ctx(1, T)
+        if early_stop:
+            return bool(self._ext.es_word_supported(ctx, T, self.decoding_type, self.q_bit, self.target_bits,
+                                                    KERNELS[kernel or self.kernel], self.clip))
         return bool(self._ext.word_supported(ctx, T, self.decoding_type, self.q_bit, self.target_bits,
                                              KERNELS[kernel or self.kernel], self.clip))
 
@@ -214,6 +220,55 @@ class NMSDecoder:
             nbad = int((res.word_flags == 0x80).sum().item())
             if nbad:
                 raise ValueError(f"hard_last: {nbad} frames are in packs with LLRs off the quantizer "
+                                 "grid and were not decoded (on_off_grid='mark' returns them marked)")
+            if not word_flags:
+                res.word_flags = None
+        return res
+
+    def _decode_es_word(self, llr, B, T, nt, hard_last, word_flags, counters, flags, n_iter, iter_hist,
+                        kernel, stream, on_off_grid, channel=None):
+        """``decode(early_stop=True, hard_last=...)`` and, with ``channel`` (sigma, seed, offset,
+        punct, short) instead of ``llr``, ``decode_awgn``'s: each frame's decoded word at its stop
+        iteration beside the early-stop outputs."""
+        torch = self._torch
+        dev = self.device
+        if on_off_grid not in ("raise", "mark"):
+            raise ValueError("on_off_grid must be 'raise' or 'mark'")
+        nw = (self.n_vars + 31) // 32
+        res = DecodeResult()
+        if isinstance(hard_last, torch.Tensor):             # caller-owned int32 [>= B, nw]
+            if (hard_last.dtype != torch.int32 or hard_last.device != dev or hard_last.dim() != 2 or
+                    hard_last.shape[0] < B or hard_last.shape[1] != nw or not hard_last.is_contiguous()):
+                raise ValueError(f"hard_last must be a contiguous int32 [>= B, {nw}] tensor on the decoder's device")
+            res.hard_last = hard_last
+        else:
+            res.hard_last = torch.empty((B, nw), dtype=torch.int32, device=dev)
+        # (the generated channel is always on the grid)
+        want_wf = word_flags or (on_off_grid == "raise" and channel is None)
+        if want_wf:
+            res.word_flags = torch.empty(B, dtype=torch.uint8, device=dev)
+        self._es_outputs(res, B, T, counters, flags, n_iter, iter_hist)
+        if B == 0:
+            return res
+        ctx = self._ensure_ctx(B, T)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        ptr = lambda t: 0 if t is None else t.data_ptr()   # noqa: E731
+        outs = (res.hard_last.data_ptr(), ptr(res.word_flags), ptr(res.counters), ptr(res.flags),
+                ptr(res.n_iter), ptr(res.iter_hist), stream.cuda_stream)
+        if channel is not None:
+            sigma, seed, offset, punct, short = channel
+            self._ext.decode_awgn_es_word(ctx, B, T, self.decoding_type, self.q_bit, nt, self.clip,
+                                          KERNELS[kernel or self.kernel], float(sigma), int(seed), int(offset),
+                                          int(punct[0]), int(punct[1]), int(short[0]), int(short[1]), *outs)
+            return res
+        self._ext.decode_es_word(ctx, llr.data_ptr(), B, T, self.decoding_type, self.q_bit, nt, self.clip,
+                                 KERNELS[kernel or self.kernel], *outs)
+        if on_off_grid == "raise":
+            stream.synchronize()
+            nbad = int((res.word_flags == 0x80).sum().item())
+            if nbad:
+                raise ValueError(f"early_stop: {nbad} frames are in packs with LLRs off the quantizer "
                                  "grid and were not decoded (on_off_grid='mark' returns them marked)")
             if not word_flags:
                 res.word_flags = None
@@ -280,17 +335,29 @@ class NMSDecoder:
         over all N*z variables, packed as ``hard[T-1]`` is -- from the bit-sliced kernels' own
         launch, with ``counters`` / ``flags`` as a plain decode gives them and, with
         ``word_flags=True``, a uint8 [B] whose bit 0 says the word's syndrome is nonzero.  ``app``
-        defaults to False; ``app`` / ``hard`` / ``synd`` / ``iter_wrong`` / ``early_stop`` are not
-        served with it and raise ``ValueError``.  The LLRs must lie on the quantizer grid, as for
-        ``early_stop``: a pack of 32 frames holding an off-grid value is not decoded (zero rows,
-        ``word_flags`` and ``flags`` 0x80, not counted); ``on_off_grid`` as above."""
+        defaults to False; ``app`` / ``hard`` / ``synd`` / ``iter_wrong`` are not served with it and
+        raise ``ValueError``.  The LLRs must lie on the quantizer grid, as for ``early_stop``: a
+        pack of 32 frames holding an off-grid value is not decoded (zero rows, ``word_flags`` and
+        ``flags`` 0x80, not counted); ``on_off_grid`` as above.
+
+        ``early_stop=True`` with ``hard_last``: ``res.hard_last`` then holds each
+        frame's word at the iteration it stopped at, ``hd_stop`` -- what a practical decoder
+        returns -- not the last iteration's: frozen at the frame's first zero-syndrome iteration,
+        iteration T - 1's for a frame that never stops.  ``word_flags`` bit 0 is then 0 for every
+        frame with ``n_iter < T``; ``counters`` / ``flags`` / ``n_iter`` / ``iter_hist`` are those of
+        ``early_stop=True`` alone."""
         torch = self._torch
         T = self.T if T is None else int(T)
         nt = self.target_bits if target_bits is None else int(target_bits)
         if T > self.T:
             raise ValueError(f"T={T} exceeds the {self.T} iterations the weights cover")
+        if hard_last is not False and hard_last is not None and early_stop:
+            self._es_check_exports(app=app, hard=hard, synd=synd, iter_wrong=iter_wrong)
+            llr = self._as_llr(llr)
+            return self._decode_es_word(llr, int(llr.shape[0]), T, nt, hard_last, word_flags, counters, flags,
+                                        n_iter, iter_hist, kernel, stream, on_off_grid)
         if hard_last is not False and hard_last is not None:
-            bad = [k for k, v in dict(app=app, hard=hard, synd=synd, iter_wrong=iter_wrong, early_stop=early_stop,
+            bad = [k for k, v in dict(app=app, hard=hard, synd=synd, iter_wrong=iter_wrong,
                                       n_iter=n_iter, iter_hist=iter_hist is not None and iter_hist is not False).items() if v]
             if bad:
                 raise ValueError("hard_last serves word_flags, counters and flags only, not " + ", ".join(bad))
@@ -406,15 +473,21 @@ class NMSDecoder:
                     T: Optional[int] = None, app: bool = False, counters=None, flags=None,
                     kernel: Optional[str] = None, stream=None, iter_wrong: bool = False,
                     early_stop: bool = False, n_iter: bool = False, iter_hist=None,
-                    hard_last=False) -> DecodeResult:
+                    hard_last=False, word_flags: bool = False) -> DecodeResult:
         """Decode B codewords whose LLRs come from the on-GPU AWGN channel, generated inside
         the decoder (``ldpc_decode_awgn``): identical to ``decode(awgn(...))`` without the
         LLRs ever being written to HBM.  ``counters`` / ``flags`` as in ``decode``;
         ``early_stop`` / ``n_iter`` / ``iter_hist`` as in ``decode`` (the generated channel is
-        always on the grid).  ``hard_last`` is not served here (the kernels' in-prologue channel
-        has no export build) and raises ``ValueError``: compose ``awgn()`` and ``decode()``."""
-        if hard_last is not False and hard_last is not None:
+        always on the grid).  ``hard_last`` / ``word_flags`` are served with ``early_stop=True``
+        (each frame's word at its stop iteration, as ``decode(early_stop=True, hard_last=...)``;
+        DESIGN.md 3.9).  Without ``early_stop``, ``hard_last`` is not served here (the kernels'
+        in-prologue channel has no export build) and raises ``ValueError``: compose ``awgn()`` and
+        ``decode()``."""
+        want_word = hard_last is not False and hard_last is not None
+        if want_word and not early_stop:
             raise ValueError("decode_awgn does not serve hard_last: use decode(awgn(...), hard_last=True)")
+        if word_flags and not want_word:
+            raise ValueError("word_flags is an output of hard_last=True")
         torch = self._torch
         T = self.T if T is None else int(T)
         punct = getattr(self, "punct", (0, 0)) if punct is None else punct
@@ -424,6 +497,10 @@ class NMSDecoder:
             if T > self.T:
                 raise ValueError(f"T={T} exceeds the {self.T} iterations the weights cover")
             B = int(B)
+            if want_word:
+                return self._decode_es_word(None, B, T, self.target_bits, hard_last, word_flags, counters, flags,
+                                            n_iter, iter_hist, kernel, stream, "mark",
+                                            channel=(sigma, seed, offset, punct, short))
             res = DecodeResult()
             if B == 0:
                 return self._es_outputs(res, 0, T, counters, flags, n_iter, iter_hist)

@@ -4,11 +4,16 @@
 pack-maximum iterations, the histogram and both modes' frame errors, one JSON line each and
 ``<out>/sweep_step.json``.
 
-  python tools/early_stop_step.py [out_dir] [--points CONFIG:SNR,SNR,... ...] [--batch B]
+  python tools/early_stop_step.py [out_dir] [--points CONFIG:SNR,SNR,... ...] [--batch B] [--word]
 
   out_dir   default bench_out/, which git ignores
   --points  the configs (bench.py's) and their SNRs in dB; default C2:3.5,5.0,6.5 C3:4.5,6.0;
             C5 alone: --points C5:3.0,8.0,14.5
+  --word    also time the early-stop decode that returns each frame's word at its stop iteration
+            (``decode_awgn(early_stop=True, hard_last=..., word_flags=True)``, DESIGN.md 3.9:
+            ``es_word_*``) and the full-T word mode on the same channel's LLRs resident in HBM
+            (``decode(llr, hard_last=...)``, 3.8: ``word_full_*``), and check the early-stop
+            outputs of the two early-stop modes against each other
 """
 import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,6 +25,7 @@ def parse(argv=None):
     ap.add_argument("out", nargs="?", default=os.path.join(ROOT, "bench_out"))
     ap.add_argument("--points", nargs="+", default=["C2:3.5,5.0,6.5", "C3:4.5,6.0"], metavar="CONFIG:SNRS")
     ap.add_argument("--batch", type=int, default=1 << 20, help="codewords per decode")
+    ap.add_argument("--word", action="store_true", help="also time the two decoded-word modes")
     a = ap.parse_args(argv)
     pts = []
     for p in a.points:
@@ -82,6 +88,41 @@ def main(argv=None):
                     out["pack_max_mean"] = round(float(pm.mean()), 3)
                     out["pack_max_max"] = int(pm.max())
                     out["iter_hist"] = [int(x) for x in h]
+            if a.word:
+                assert dec.supports_hard_last(early_stop=True), config
+                hl = torch.empty((B, (dec.n_vars + 31) // 32), dtype=torch.int32, device=dev)
+                llr = dec.awgn(B, sigma, 11)
+
+                def run_word(es, seed=11):
+                    cnt = torch.zeros(4, dtype=torch.int64, device=dev)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    if es:
+                        r = dec.decode_awgn(B, sigma, seed, counters=cnt, early_stop=True, iter_hist=True,
+                                            n_iter=True, hard_last=hl, word_flags=True)
+                    else:
+                        r = dec.decode(llr, counters=cnt, hard_last=hl, word_flags=True, on_off_grid="mark")
+                    e1.record()
+                    torch.cuda.synchronize()
+                    return e0.elapsed_time(e1), r
+                for es in (True, False):
+                    for w in range(2):
+                        run_word(es)
+                    ts = []
+                    for k in range(5):
+                        t, rw = run_word(es)
+                        ts.append(t)
+                    tag = "es_word" if es else "word_full"
+                    out[tag + "_ms"] = [round(x, 3) for x in ts]
+                    out[tag + "_ms_median"] = round(float(np.median(ts)), 3)
+                    out[tag + "_kernel"] = dec.last_kernel()
+                    out[tag + "_not_codeword"] = int((rw.word_flags & 1).sum().item())
+                    if es:      # (r: the early-stop decode of the same seed, above)
+                        same = all(torch.equal(getattr(rw, k), getattr(r, k)) for k in ("counters", "n_iter", "iter_hist"))
+                        out["es_word_equals_es"] = bool(same)
+                        assert same, "the early-stop outputs of the two early-stop modes differ"
+                        out["es_word_nonzero_rows"] = int((hl != 0).any(dim=1).sum().item())
+                del llr, hl
             print(json.dumps(out), flush=True)
             rows.append(out)
     os.makedirs(a.out, exist_ok=True)
