@@ -12,7 +12,7 @@
 #include <utility>
 #include <vector>
 
-#include "ldpc_bs_kernel.h"
+#include "ldpc_bs_host.h"
 
 namespace ldpc {
 namespace bs {
@@ -63,7 +63,7 @@ __global__ void k_bs_tables(const float* __restrict__ alpha, const float* __rest
 }
 
 // ---- host: planning, graph tables, launch -------------------------------------------------
-typedef int (*LaunchFn)(const BsArgs&, int, int, size_t, hipStream_t, bool, int, int*);
+typedef int (*LaunchFn)(const BsLaunch&, int, int, size_t, hipStream_t, bool, int, int*);
 template <int... I>
 constexpr auto launch_table(std::integer_sequence<int, I...>) {
     return std::array<LaunchFn, sizeof...(I)>{&bs_launch<I>...};
@@ -267,28 +267,6 @@ BsPlan bs_plan(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float cli
     return p;
 }
 
-}  // namespace bs
-
-using namespace bs;
-
-bool bs_supported(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T) {
-    return bs_plan(g, mode, ucn, per_edge_w, clip, T).ok || bsc_supported(g, mode, ucn, per_edge_w, clip, T);
-}
-
-const char* bs_kernel_name(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T) {
-    static thread_local char buf[64];
-    const BsPlan p = bs_plan(g, mode, ucn, per_edge_w, clip, T);
-    if (!p.ok) return bsc_kernel_name(g, mode, ucn, per_edge_w, clip, T);
-    const BsInst& k = kBsInst[p.inst];
-    if (k.VPL == 1 && k.CPL == 1)
-        snprintf(buf, sizeof(buf), "bsl[p32,w%d,d%d,v%d,l%d%s]", p.nw, k.D, k.DV, k.LPC, p.ucn ? ",ucn" : "");
-    else
-        snprintf(buf, sizeof(buf), "bsl[p32,w%d,d%d,v%d,l%d,x%d/%d%s]", p.nw, k.D, k.DV, k.LPC, k.VPL,
-                 k.CPL, p.ucn ? ",ucn" : "");
-    return buf;
-}
-
-namespace bs {
 // Deal `n` chunks (costs `cost`) to nw waves with at most `cap` chunks per wave (slot[w][c] =
 // chunk or -1; wave w runs on SIMD w mod 4).  The chunks of one phase end at a barrier, and a
 // SIMD's last busy wave runs alone, latency-bound (a dependent chain issues every ~8.5 cycles
@@ -534,12 +512,8 @@ int bs_make_tables(const Bufs& b, const DevGraph& g, int arows, int ar, int bcol
     const size_t na = (size_t)b.T * ar * LUT_W, nb = (size_t)b.T * bcols * BLUT_W;
     const size_t bytes = (na + nb) * 4;
     if (bytes > ws.bs_lut_bytes) {
-        if (ws.bs_lut) (void)hipFree(ws.bs_lut);
-        ws.bs_lut = nullptr;
-        ws.bs_lut_bytes = 0;
         ws.key_bslut[0] = ~0ull;
-        if (hipMalloc(&ws.bs_lut, bytes) != hipSuccess) { (void)hipGetLastError(); return LDPC_ERR_OOM; }
-        ws.bs_lut_bytes = bytes;
+        if (dev_grow(ws.bs_lut, ws.bs_lut_bytes, bytes, 1) != LDPC_OK) return LDPC_ERR_OOM;
     }
     *alut = reinterpret_cast<uint32_t*>(ws.bs_lut);
     *blut = *alut + na;
@@ -558,6 +532,8 @@ int bs_make_tables(const Bufs& b, const DevGraph& g, int arows, int ar, int bcol
     return hipGetLastError() == hipSuccess ? LDPC_OK : LDPC_ERR_HIP;
 }
 }  // namespace bs
+
+using namespace bs;
 
 // graph tables, built on the host (bs_graph_tables uploads them once per context)
 struct BsHostTables {
@@ -750,54 +726,67 @@ static int bs_graph_tables(const DevGraph& g, const BsPlan& p, void*& graph, int
     return LDPC_OK;
 }
 
-bool bs_q8_ok(const DevGraph& g, int mode, bool ucn, float clip, int T, bool has_short) {
-    const BsPlan p = bs_plan(g, mode, ucn, false, clip, T);
-    if (!p.ok) return bsc_q8_ok(g, mode, ucn, clip, T, has_short);
+// ---- requests (ldpc_fused.h) -----------------------------------------------------------------
+// Where a request goes: its bsl plan, or without one (!ok) *to_bsc: the compressed kernel
+// (ldpc_bsc.hip) gets it.  A request without early stop falls through whenever no bsl plan serves
+// it.  An early-stop request only where no bsl plan AT ALL serves the graph, which is
+// where its full-T decodes run on bsc.  (A graph that a multi-chunk bsl instance serves, 5G BG2,
+// would fit bsc too, but its decodes never run there, and it has no early-stop build.)
+static BsPlan bs_route(const DevGraph& g, const BsReq& r, bool* to_bsc) {
+    BsPlan p = bs_plan(g, r.mode, r.ucn, r.per_edge_w, r.clip, r.T, r.es);
+    *to_bsc = !p.ok && (!r.es || !bs_plan(g, r.mode, r.ucn, r.per_edge_w, r.clip, r.T).ok);
+    return p;
+}
+
+bool bs_supported(const DevGraph& g, const BsReq& r) {
+    bool to_bsc;
+    return bs_route(g, r, &to_bsc).ok || (to_bsc && bsc_supported(g, r));
+}
+
+bool bs_q8_ok(const DevGraph& g, const BsReq& r, bool has_short) {
+    bool to_bsc;
+    const BsPlan p = bs_route(g, r, &to_bsc);
+    if (!p.ok) return to_bsc && bsc_q8_ok(g, r, has_short);
     // (the in-prologue channel's tables borrow the slot region)
     return (!has_short || p.cu > 0.f) && q8_tab_fits(p);
 }
 
-// one launch of plan p; es: the early-stop outputs (an ES instance's plan), else null
-// (hdw: the plane buffer of the stop-iteration words, or null: DESIGN 3.9)
-struct EsOut { uint8_t* n_iter; int64_t* iter_hist; uint32_t* hdw; };
-static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const BsPlan& p, const float* llr, int mode,
-                  bool ucn, int64_t* counters, uint8_t* flags, uint32_t* bad, uint32_t* hdx, bool word,
-                  const EsOut* es, hipStream_t s) {
-    int st = es ? bs_graph_tables(g, p, ws.bs_es_graph, ws.bs_es_graph_inst, s)
-                : bs_graph_tables(g, p, ws.bs_graph, ws.bs_graph_inst, s);
+const char* bs_kernel_name(const DevGraph& g, const BsReq& r) {
+    static thread_local char buf[64];
+    bool to_bsc;
+    const BsPlan p = bs_route(g, r, &to_bsc);
+    if (!p.ok) return to_bsc ? bsc_kernel_name(g, r) : "";
+    const BsInst& k = kBsInst[p.inst];
+    char x[16] = "";
+    if (k.VPL > 1 || k.CPL > 1) snprintf(x, sizeof(x), ",x%d/%d", k.VPL, k.CPL);
+    snprintf(buf, sizeof(buf), "bsl[p32,w%d,d%d,v%d,l%d%s%s%s]", p.nw, k.D, k.DV, k.LPC, x, p.ucn ? ",ucn" : "",
+             r.es ? ",es" : "");
+    return buf;
+}
+
+// one launch of plan p (an ES instance's plan for an early-stop request)
+static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const BsPlan& p, const float* llr,
+                  const BsReq& r, const BsOut& o, hipStream_t s) {
+    // (the early-stop instances' graph tables: a pair of their own)
+    void*& graph = r.es ? ws.bs_es_graph : ws.bs_graph;
+    int st = bs_graph_tables(g, p, graph, r.es ? ws.bs_es_graph_inst : ws.bs_graph_inst, s);
     if (st != LDPC_OK) return st;
     const BsInst& k = kBsInst[p.inst];
-    const float step = mode_step_bs(mode);
+    const float step = mode_step_bs(r.mode);
     const int ar = (k.UCN ? 2 : 1) * p.arows;
     uint32_t *alut = nullptr, *blut = nullptr;
-    st = bs_make_tables(b, g, p.arows, ar, p.bcols, step, bs_qmax(mode), p.cu, ucn, ws, &alut, &blut, s);
+    st = bs_make_tables(b, g, p.arows, ar, p.bcols, step, bs_qmax(r.mode), p.cu, r.ucn, ws, &alut, &blut, s);
     if (st != LDPC_OK) return st;
     const int DV = k.DV;
     const int VNW = (k.PK ? (DV + 1) / 2 : DV) + 1;
-    const uint32_t* gt = reinterpret_cast<const uint32_t*>(es ? ws.bs_es_graph : ws.bs_graph);
-    // (BsArgs, and the early-stop builds' additions: an ES instance's launch reads them, every
-    // other launch takes the BsArgs base alone)
-    BsArgsEw a{};
-    if (es) {
-        a.n_iter = es->n_iter;
-        a.iter_hist = es->iter_hist;
-        a.hdw = es->hdw;
-    }
+    const uint32_t* gt = reinterpret_cast<const uint32_t*>(graph);
+    BsLaunch a{};
+    a.n_iter = o.n_iter;
+    a.iter_hist = o.iter_hist;
+    a.hdw = o.hdw;
+    a.word = o.word ? 1 : 0;
     a.llr = llr;
-    if (b.q8) {                          // the in-prologue channel (ldpc_decode_awgn)
-        const AwgnParams& g8 = *reinterpret_cast<const AwgnParams*>(b.gen8);
-        a.gen.tab = b.q8;
-        a.gen.k0 = g8.k0;
-        a.gen.k1 = g8.k1;
-        a.gen.offset = g8.offset;
-        a.gen.nb = g8.nb;
-        a.gen.kmin = g8.kmin;
-        a.gen.ps = g8.ps;
-        a.gen.pe = g8.pe;
-        a.gen.ss = g8.ss;
-        a.gen.se = g8.se;
-        a.gen.lds = q8_tab_lds(p);
-    }
+    a.gen = bs_gen(b, q8_tab_lds(p));    // the in-prologue channel (ldpc_decode_awgn)
     a.B = b.B;
     a.n_vars = g.n_vars;
     a.n_checks = g.n_checks;
@@ -810,7 +799,7 @@ static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const Bs
     a.fold_wave = p.cn_lanes < 64 * p.nw ? (uint32_t)(p.nw - 1) : (p.nw > 1 ? 1u : 0u);
     a.inv = 1.0f / step;
     a.cu = p.cu > 0.f ? p.cu : -1.f;
-    a.qmax = bs_qmax(mode);
+    a.qmax = bs_qmax(r.mode);
     a.ucn = p.ucn ? 1 : 0;
     a.ucn_iter = g.w_ucn_iter;
     a.beta_id = g.w_beta_id_mask;        // (identity on m <= 15 implies it on m <= qmax)
@@ -827,13 +816,13 @@ static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const Bs
     a.arows = p.arows;
     a.bcols = p.bcols;
     // the fixed-set channel tables cover the grids whose magnitudes saturate at 15 (q = 5, -5)
-    a.btid = (bs_qmax(mode) == QMAX && !getenv("LDPC_BS_NOBFIX")) ? g.beta_tid : nullptr;
+    a.btid = (bs_qmax(r.mode) == QMAX && !getenv("LDPC_BS_NOBFIX")) ? g.beta_tid : nullptr;
     a.btid_n = g.N;
-    a.counters = counters;
-    a.flags = flags;
-    a.bad = bad;
-    a.iter_wrong = es ? nullptr : b.iter_wrong;
-    a.hdx = hdx;
+    a.counters = o.counters;
+    a.flags = o.flags;
+    a.bad = o.bad;
+    a.iter_wrong = r.es ? nullptr : b.iter_wrong;
+    a.hdx = o.hdx;
     bs_stagger(k.VPL > 1 || k.CPL > 1, &a.stagger, &a.stagger_n);
     a.off_slots = p.off_slots;
     a.off_pad = p.off_pad;
@@ -845,14 +834,6 @@ static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const Bs
     a.off_hdl = p.off_hdl;
     a.off_ch = p.off_ch;
     if (const char* e = getenv("LDPC_DIAG_ABLATE")) a.ablate = atoi(e);   // -DBS_DIAG builds
-    // (an export launch: BsArgsXp, the word mode's switch after the BsArgs base)
-    BsArgsXp ax{};
-    const BsArgs* ap = &a;
-    if (hdx) {
-        static_cast<BsArgs&>(ax) = a;
-        ax.word = word ? 1 : 0;
-        ap = &ax;
-    }
     const int npacks = (int)((b.B + PACK - 1) / PACK);
     // the workgroups of the instances with the pack loop (ldpc_bs_kernel.h, bs_loops): by default
     // those resident at once (asked once per context, instance and LDS size: ws.bs_resident);
@@ -874,8 +855,8 @@ static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const Bs
     static unsigned long long* dst = nullptr;
     if (!dst && hipMalloc(reinterpret_cast<void**>(&dst), 256 * 8) != hipSuccess) return LDPC_ERR_OOM;
     if (hipMemsetAsync(dst, 0, 256 * 8, s) != hipSuccess) return LDPC_ERR_HIP;
-    a.stamps = ax.stamps = dst;
-    st = kLaunch[p.inst](*ap, npacks, p.nw, lds, s, b.q8 != nullptr, grid, ws.bs_resident);
+    a.stamps = dst;
+    st = kLaunch[p.inst](a, npacks, p.nw, lds, s, b.q8 != nullptr, grid, ws.bs_resident);
     unsigned long long hst[256];
     if (st != LDPC_OK || hipMemcpyAsync(hst, dst, sizeof(hst), hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
@@ -892,74 +873,16 @@ static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const Bs
     }
     return st;
 #else
-    return kLaunch[p.inst](*ap, npacks, p.nw, lds, s, b.q8 != nullptr, grid, ws.bs_resident);
+    return kLaunch[p.inst](a, npacks, p.nw, lds, s, b.q8 != nullptr, grid, ws.bs_resident);
 #endif
 }
 
-int bs_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode,
-              bool ucn, int64_t* counters, uint8_t* flags, uint32_t* bad, uint32_t* hdx, bool word, hipStream_t s) {
-    const BsPlan p = bs_plan(g, mode, ucn, false, b.clip, b.T);
-    if (!p.ok) return bsc_decode(g, b, ws, llr, mode, ucn, counters, flags, bad, hdx, word, s);
-    return bs_run(g, b, ws, p, llr, mode, ucn, counters, flags, bad, hdx, word, nullptr, s);
-}
-
-// ---- early stop ---------------------------------------------------------------
-// The compressed kernel's early-stop builds (bsc_*_es) serve the request exactly where bs_decode
-// falls through to bsc_decode: when no bsl plan at all serves the graph.  (A graph that a
-// multi-chunk bsl instance serves, 5G BG2, would fit bsc too, but its decodes never run there: it
-// has no early-stop build.)
-static bool es_falls_to_bsc(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T) {
-    return !bs_plan(g, mode, ucn, per_edge_w, clip, T).ok;
-}
-bool bs_es_supported(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T) {
-    if (bs_plan(g, mode, ucn, per_edge_w, clip, T, true).ok) return true;
-    return es_falls_to_bsc(g, mode, ucn, per_edge_w, clip, T) && bsc_es_supported(g, mode, ucn, per_edge_w, clip, T);
-}
-bool bs_es_q8_ok(const DevGraph& g, int mode, bool ucn, float clip, int T, bool has_short) {
-    const BsPlan p = bs_plan(g, mode, ucn, false, clip, T, true);
-    if (!p.ok) return es_falls_to_bsc(g, mode, ucn, false, clip, T) && bsc_es_q8_ok(g, mode, ucn, clip, T, has_short);
-    return (!has_short || p.cu > 0.f) && q8_tab_fits(p);
-}
-const char* bs_es_kernel_name(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T) {
-    static thread_local char buf[64];
-    const BsPlan p = bs_plan(g, mode, ucn, per_edge_w, clip, T, true);
-    if (!p.ok)
-        return es_falls_to_bsc(g, mode, ucn, per_edge_w, clip, T) ? bsc_es_kernel_name(g, mode, ucn, per_edge_w, clip, T) : "";
-    const BsInst& k = kBsInst[p.inst];
-    snprintf(buf, sizeof(buf), "bsl[p32,w%d,d%d,v%d,l%d%s,es]", p.nw, k.D, k.DV, k.LPC, p.ucn ? ",ucn" : "");
-    return buf;
-}
-// the early-stop decode of b.B codewords (LLRs at llr, or the in-prologue channel b.q8 / b.gen8):
-// counters [0..2], frame flags, n_iter [B] and iter_hist [T], each or null.  Packs with an LLR off
-// the grid are marked (flags 0x80, n_iter 0), not decoded.  LDPC_ERR_UNSUPPORTED: no ES instance
-// serves the request; nothing was launched.  hdw: null, or [packs][n_vars] u32 that takes each
-// codeword's hard decisions at its stop iteration (the EW builds; ws.bs_bad then holds the packs'
-// off-grid marks for word_out).
-int bs_decode_es(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode, bool ucn,
-                 int ntiles_max, int64_t* counters, uint8_t* flags, uint8_t* n_iter, int64_t* iter_hist,
-                 uint32_t* hdw, hipStream_t s) {
-    const BsPlan p = bs_plan(g, mode, ucn, false, b.clip, b.T, true);
-    // (no bsl plan at all: the compressed kernel's early-stop builds, as bs_decode's fall-through)
-    const bool to_bsc = !p.ok && es_falls_to_bsc(g, mode, ucn, false, b.clip, b.T) &&
-                        bsc_es_supported(g, mode, ucn, false, b.clip, b.T);
-    if (!p.ok && !to_bsc) return LDPC_ERR_UNSUPPORTED;
-    if (b.q8 && !bs_es_q8_ok(g, mode, ucn, b.clip, b.T, reinterpret_cast<const AwgnParams*>(b.gen8)->ss > 0))
-        return LDPC_ERR_UNSUPPORTED;
-    const int64_t npk = (b.B + 31) / 32;
-    if (npk > ws.bs_bad_n) {             // (the kernel's per-pack off-grid word, as bs_decode's)
-        if (ws.bs_bad) (void)hipFree(ws.bs_bad);
-        ws.bs_bad = nullptr;
-        ws.bs_bad_n = 0;
-        const int64_t n = std::max<int64_t>(npk, (int64_t)ntiles_max * 8);
-        if (hipMalloc(reinterpret_cast<void**>(&ws.bs_bad), (size_t)n * 4) != hipSuccess) {
-            (void)hipGetLastError();
-            return LDPC_ERR_OOM;
-        }
-        ws.bs_bad_n = n;
-    }
-    if (to_bsc) return bsc_decode_es(g, b, ws, llr, mode, ucn, counters, flags, ws.bs_bad, n_iter, iter_hist, hdw, s);
-    const EsOut es{n_iter, iter_hist, hdw};
-    return bs_run(g, b, ws, p, llr, mode, ucn, counters, flags, ws.bs_bad, nullptr, false, &es, s);
+int bs_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, const BsReq& r,
+              const BsOut& o, hipStream_t s) {
+    bool to_bsc;
+    const BsPlan p = bs_route(g, r, &to_bsc);
+    if (!p.ok) return to_bsc ? bsc_decode(g, b, ws, llr, r, o, s) : LDPC_ERR_UNSUPPORTED;
+    return bs_run(g, b, ws, p, llr, r, o, s);
 }
 
 }  // namespace ldpc

@@ -1718,26 +1718,52 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
 #undef BS_ST
 }
 
+// ---- launch ---------------------------------------------------------------------------------
+// What the host fills for one launch (bs_run): the arguments of every build of an instance -- BsArgs,
+// the early-stop builds' additions and the export builds' word switch.  A launcher hands its kernel
+// the argument struct that kernel takes, built from this one (bs_launch_kernel).
+struct BsLaunch : BsArgsEw {
+    int word;                    // BsArgsXp::word
+};
+
+template <class K>
+K kernel_arg_of(void (*)(K));    // (the argument struct of a kernel, for decltype)
+// the kernel-argument struct K from the host's struct: that base of it (BsArgs, BsArgsEs,
+// BsArgsEw) or, for the export builds' K, the BsArgs base and the word switch; bsc's alike
+template <class K, class L>
+K bs_kernel_args(const L& a) {
+    if constexpr (std::is_base_of_v<K, L>) return a;
+    else return K{a, a.word};
+}
+// every build may ask for all of BS_LDS_MAX as dynamic LDS: set once per kernel
+template <auto Fn>
+void bs_max_lds() {
+    static const hipError_t once = hipFuncSetAttribute(reinterpret_cast<const void*>(Fn),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)BS_LDS_MAX);
+    (void)once;
+}
+// one launch of the build Fn (of either bit-sliced kernel) with nw waves per workgroup
+template <auto Fn, class L>
+int bs_launch_kernel(const L& a, int nblocks, int nw, size_t lds, hipStream_t s) {
+    bs_max_lds<Fn>();
+    hipLaunchKernelGGL(Fn, dim3(nblocks), dim3(64 * nw), lds, s, bs_kernel_args<decltype(kernel_arg_of(Fn))>(a));
+    return hipGetLastError() == hipSuccess ? LDPC_OK : LDPC_ERR_HIP;
+}
+
 // grid: the workgroups launched; the instances with the pack loop (bs_loops) take any count from 1
 // to the packs, the others exactly one per pack.  *resident (ldpc_bs.hip: one word per context and
 // build): the workgroups of this instance, workgroup size and LDS size that fit the device at
 // once, asked from the runtime when it is 0.
 template <int I, bool XP, bool Q8>
-int launch_bs_x(const BsArgs& a, int npacks, int nw, size_t lds, hipStream_t s, int grid, int* resident) {
+int launch_bs_x(const BsLaunch& a, int npacks, int nw, size_t lds, hipStream_t s, int grid, int* resident) {
     constexpr BsInst k = kBsInst[I];
     static_assert(bs_loops(k) == (BS_LOOP_TU != 0), "BS_LOOP_TU lists the instances of bs_loops");
-    constexpr int LB = 1024;
-    auto* fn = &k_bs<k.D, k.DV, k.LPC, k.VPL, k.CPL, k.UCN, k.BIG, k.PK, k.WPE, XP, LB, Q8>;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)BS_LDS_MAX);
-        attr = true;
-    }
+    constexpr auto fn = &k_bs<k.D, k.DV, k.LPC, k.VPL, k.CPL, k.UCN, k.BIG, k.PK, k.WPE, XP, 1024, Q8>;
     int nblocks = npacks;
     if constexpr (bs_loops(k)) {
         if (grid < 0) {                      // (no LDPC_BS_GRID: the resident workgroups)
             if (*resident <= 0) {
+                bs_max_lds<fn>();
                 int dev = 0, ncu = 0, per_cu = 0;
                 if (hipGetDevice(&dev) != hipSuccess ||
                     hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
@@ -1753,58 +1779,41 @@ int launch_bs_x(const BsArgs& a, int npacks, int nw, size_t lds, hipStream_t s, 
         }
         if (grid > 0 && grid < npacks) nblocks = grid;
     }
-    // (an export launch is handed BsArgsXp, passed as its BsArgs base: bs_run)
-    if constexpr (XP) hipLaunchKernelGGL(fn, dim3(nblocks), dim3(64 * nw), lds, s, static_cast<const BsArgsXp&>(a));
-    else hipLaunchKernelGGL(fn, dim3(nblocks), dim3(64 * nw), lds, s, a);
-    return hipGetLastError() == hipSuccess ? LDPC_OK : LDPC_ERR_HIP;
-}
-template <int I>
-int launch_bs(const BsArgs& a, int npacks, int nw, size_t lds, hipStream_t s, bool q8, int grid, int* resident) {
-    // (the generated channel comes from ldpc_decode_awgn, which exports no hard bits)
-    // (resident[0 / 1 / 2]: the decode, the hard-bit export and the in-prologue channel build)
-    if (a.hdx) return q8 ? LDPC_ERR_UNSUPPORTED : launch_bs_x<I, true, false>(a, npacks, nw, lds, s, grid, resident + 1);
-    return q8 ? launch_bs_x<I, false, true>(a, npacks, nw, lds, s, grid, resident + 2)
-              : launch_bs_x<I, false, false>(a, npacks, nw, lds, s, grid, resident);
+    return bs_launch_kernel<fn>(a, nblocks, nw, lds, s);
 }
 
 // the early-stop builds of an ES instance (float LLRs, or the in-prologue channel): one workgroup
 // per pack, no pack loop (packs end at different times) and no export build
 template <int I, bool Q8, bool EW>
-int launch_bs_es_x(const std::conditional_t<EW, BsArgsEw, BsArgsEs>& a, int npacks, int nw, size_t lds, hipStream_t s) {
+int launch_bs_es_x(const BsLaunch& a, int npacks, int nw, size_t lds, hipStream_t s) {
     constexpr BsInst k = kBsInst[I];
     static_assert(k.ES && !bs_loops(k), "an early-stop instance");
-    auto* fn = &k_bs<k.D, k.DV, k.LPC, k.VPL, k.CPL, k.UCN, k.BIG, k.PK, k.WPE, false, 1024, Q8, true, EW>;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)BS_LDS_MAX);
-        attr = true;
-    }
-    hipLaunchKernelGGL(fn, dim3(npacks), dim3(64 * nw), lds, s, a);
-    return hipGetLastError() == hipSuccess ? LDPC_OK : LDPC_ERR_HIP;
+    return bs_launch_kernel<&k_bs<k.D, k.DV, k.LPC, k.VPL, k.CPL, k.UCN, k.BIG, k.PK, k.WPE, false, 1024, Q8, true, EW>>(
+        a, npacks, nw, lds, s);
 }
-// instance I's launch: an ES instance is handed the early-stop arguments (BsArgsEw, passed as
-// their BsArgs base) and has no other build; the others never see them
+// instance I's launch: an ES instance has the early-stop builds alone (with a plane buffer for the
+// stop-iteration words, the EW build: DESIGN 3.9); the others never see the early-stop arguments
 template <int I>
-int launch_bs_any(const BsArgs& a, int npacks, int nw, size_t lds, hipStream_t s, bool q8, int grid, int* resident) {
+int launch_bs_any(const BsLaunch& a, int npacks, int nw, size_t lds, hipStream_t s, bool q8, int grid, int* resident) {
     if constexpr (kBsInst[I].ES) {
         if (a.hdx) return LDPC_ERR_UNSUPPORTED;
-        const BsArgsEw& aw = static_cast<const BsArgsEw&>(a);
-        // (with a plane buffer for the stop-iteration words, the EW build: DESIGN 3.9)
-        if (aw.hdw)
-            return q8 ? launch_bs_es_x<I, true, true>(aw, npacks, nw, lds, s)
-                      : launch_bs_es_x<I, false, true>(aw, npacks, nw, lds, s);
-        const BsArgsEs& ae = aw;
-        return q8 ? launch_bs_es_x<I, true, false>(ae, npacks, nw, lds, s)
-                  : launch_bs_es_x<I, false, false>(ae, npacks, nw, lds, s);
+        if (a.hdw)
+            return q8 ? launch_bs_es_x<I, true, true>(a, npacks, nw, lds, s)
+                      : launch_bs_es_x<I, false, true>(a, npacks, nw, lds, s);
+        return q8 ? launch_bs_es_x<I, true, false>(a, npacks, nw, lds, s)
+                  : launch_bs_es_x<I, false, false>(a, npacks, nw, lds, s);
     } else {
-        return launch_bs<I>(a, npacks, nw, lds, s, q8, grid, resident);
+        // (the generated channel comes from ldpc_decode_awgn, which exports no hard bits)
+        // (resident[0 / 1 / 2]: the decode, the hard-bit export and the in-prologue channel build)
+        if (a.hdx) return q8 ? LDPC_ERR_UNSUPPORTED : launch_bs_x<I, true, false>(a, npacks, nw, lds, s, grid, resident + 1);
+        return q8 ? launch_bs_x<I, false, true>(a, npacks, nw, lds, s, grid, resident + 2)
+                  : launch_bs_x<I, false, false>(a, npacks, nw, lds, s, grid, resident);
     }
 }
 
 // per-instance translation units (ldpc_bs_inst.hip, -DBS_INST=i)
 template <int I>
-int bs_launch(const BsArgs& a, int npacks, int nw, size_t lds, hipStream_t s, bool q8, int grid, int* resident);
+int bs_launch(const BsLaunch& a, int npacks, int nw, size_t lds, hipStream_t s, bool q8, int grid, int* resident);
 
 }  // namespace bs
 }  // namespace ldpc

@@ -16,13 +16,15 @@
 // side needs no per-edge write-back.  Variable lanes hold several variables (VPL) and check
 // lanes several 64-lane chunks (CPL), one 16-wave workgroup per CU.
 #include <algorithm>
+#include <array>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
-#include "ldpc_bs_kernel.h"
+#include "ldpc_bs_host.h"
 
 namespace ldpc {
 namespace bs {
@@ -762,21 +764,6 @@ k_bsc(std::conditional_t<ES, std::conditional_t<EW, BscArgsEw, BscArgsEs>, std::
 namespace ldpc {
 namespace bs {
 
-std::vector<int32_t> slot_layout(const host::GraphTables& h, int LPC, size_t* nslot);
-std::vector<int32_t> slot_layout_rows(const host::GraphTables& h, const std::vector<int>& rl, size_t* nslot);
-std::vector<int32_t> uniform_lanes(const host::GraphTables& h, int LPC, int cn_lanes);
-std::vector<int> check_chunk_cost_lanes(const host::GraphTables& h, const std::vector<int32_t>& lanes);
-std::vector<int> column_rotation_lanes(const host::GraphTables& h, int EPL, const std::vector<int32_t>& lanes);
-std::vector<int> deal_chunks(const std::vector<int>& cost, int nw, int cap);
-std::vector<int> check_chunk_cost(const host::GraphTables& h, int LPC, int cch);
-std::vector<int> column_rotation(const host::GraphTables& h, int LPC, int EPL, int cn_lanes);
-void bs_stagger(bool one_per_cu, int* stagger, int* stagger_n);
-int bs_make_tables(const Bufs& b, const DevGraph& g, int arows, int ar, int bcols, float step, int qmax,
-                   float cu, bool ucn, FusedWorkspace& ws, uint32_t** alut, uint32_t** blut, hipStream_t s);
-bool bs_mode(int mode);
-float bs_step(int mode);
-int bs_qmax(int mode);
-
 constexpr int kBscNInst = sizeof(kBscInst) / sizeof(kBscInst[0]);
 constexpr int BSC_NW = 16;
 constexpr int BSC_TAG = 100;     // ws.bs_graph_inst of the bsc tables: BSC_TAG + instance
@@ -1045,54 +1032,52 @@ static int bsc_tables(const DevGraph& g, const BscPlan& p, FusedWorkspace& ws, h
     return LDPC_OK;
 }
 
-template <int I, bool XP, bool B1, bool Q8>
-static int bsc_launch1(const BscArgs& a, int nblocks, int nw, size_t lds, hipStream_t s) {
+// What bsc_run fills for one launch: the arguments of every build of an instance (as bsl's
+// BsLaunch); bs_launch_kernel hands each kernel the struct it takes.
+struct BscLaunch : BscArgsEw {
+    int word;                    // BscArgsXp::word
+};
+
+template <int I, bool XP, bool B1, bool Q8, bool ES = false, bool EW = false>
+static int bsc_launch1(const BscLaunch& a, int nblocks, int nw, size_t lds, hipStream_t s) {
     constexpr BscInst k = kBscInst[I];
-    auto* fn = &k_bsc<k.D, k.DVH, k.DVL, k.LPC, k.VPL, k.CPL, k.WPE, XP, 64 * k.NW, k.MIX, B1, Q8>;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)BS_LDS_MAX);
-        attr = true;
-    }
-    // (an export launch is handed BscArgsXp, passed as its BscArgs base: bsc_run)
-    if constexpr (XP) hipLaunchKernelGGL(fn, dim3(nblocks), dim3(64 * nw), lds, s, static_cast<const BscArgsXp&>(a));
-    else hipLaunchKernelGGL(fn, dim3(nblocks), dim3(64 * nw), lds, s, a);
-    return hipGetLastError() == hipSuccess ? LDPC_OK : LDPC_ERR_HIP;
+    return bs_launch_kernel<&k_bsc<k.D, k.DVH, k.DVL, k.LPC, k.VPL, k.CPL, k.WPE, XP, 64 * k.NW, k.MIX, B1, Q8, ES, EW>>(
+        a, nblocks, nw, lds, s);
 }
-template <int I, bool XP>
-static int bsc_launch(const BscArgs& a, int nblocks, int nw, size_t lds, hipStream_t s, bool q8) {
+// instance I's launch: the build this decode takes
+template <int I>
+static int bsc_launch(const BscLaunch& a, int nblocks, int nw, size_t lds, hipStream_t s, bool q8, bool es) {
     const bool b1 = bsc_b1_on() && a.beta_id && a.bcols == 1;
-    if constexpr (XP) {
+    if (es) {
+        // the early-stop builds (float LLRs, or the in-prologue channel): on the B1 build of the
+        // instances that have them, one workgroup per pack, no export build; with a plane buffer
+        // for the stop-iteration words, the EW build
+        if constexpr (bsc_es_inst(I)) {
+            static_assert(kBscInst[I].MIX, "an early-stop instance");
+            if (a.hdx || !a.beta_id || a.bcols != 1) return LDPC_ERR_UNSUPPORTED;
+            if (a.hdw)
+                return q8 ? bsc_launch1<I, false, true, true, true, true>(a, nblocks, nw, lds, s)
+                          : bsc_launch1<I, false, true, false, true, true>(a, nblocks, nw, lds, s);
+            return q8 ? bsc_launch1<I, false, true, true, true>(a, nblocks, nw, lds, s)
+                      : bsc_launch1<I, false, true, false, true>(a, nblocks, nw, lds, s);
+        }
+        return LDPC_ERR_UNSUPPORTED;
+    }
+    if (a.hdx) {
         // (the generated channel comes from ldpc_decode_awgn, which exports no hard bits)
         if (q8) return LDPC_ERR_UNSUPPORTED;
-    } else {
-        if (q8) return b1 ? bsc_launch1<I, false, true, true>(a, nblocks, nw, lds, s)
-                            : bsc_launch1<I, false, false, true>(a, nblocks, nw, lds, s);
+        return b1 ? bsc_launch1<I, true, true, false>(a, nblocks, nw, lds, s)
+                  : bsc_launch1<I, true, false, false>(a, nblocks, nw, lds, s);
     }
-    if (b1) return bsc_launch1<I, XP, true, false>(a, nblocks, nw, lds, s);
-    return bsc_launch1<I, XP, false, false>(a, nblocks, nw, lds, s);
+    if (q8) return b1 ? bsc_launch1<I, false, true, true>(a, nblocks, nw, lds, s)
+                      : bsc_launch1<I, false, false, true>(a, nblocks, nw, lds, s);
+    return b1 ? bsc_launch1<I, false, true, false>(a, nblocks, nw, lds, s)
+              : bsc_launch1<I, false, false, false>(a, nblocks, nw, lds, s);
 }
-// the early-stop builds of instance I (float LLRs, or the in-prologue channel): the B1 build, one
-// workgroup per pack, no export build
-template <int I, bool Q8, bool EW>
-static int bsc_launch_es1(const std::conditional_t<EW, BscArgsEw, BscArgsEs>& a, int nblocks, int nw, size_t lds, hipStream_t s) {
-    constexpr BscInst k = kBscInst[I];
-    static_assert(bsc_es_inst(I) && k.MIX, "an early-stop instance");
-    auto* fn = &k_bsc<k.D, k.DVH, k.DVL, k.LPC, k.VPL, k.CPL, k.WPE, false, 64 * k.NW, k.MIX, true, Q8, true, EW>;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)BS_LDS_MAX);
-        attr = true;
-    }
-    hipLaunchKernelGGL(fn, dim3(nblocks), dim3(64 * nw), lds, s, a);
-    return hipGetLastError() == hipSuccess ? LDPC_OK : LDPC_ERR_HIP;
-}
-// (with a plane buffer for the stop-iteration words, the EW build: DESIGN 3.9)
-template <int I, bool Q8>
-static int bsc_launch_es(const BscArgsEw& a, int nblocks, int nw, size_t lds, hipStream_t s) {
-    return a.hdw ? bsc_launch_es1<I, Q8, true>(a, nblocks, nw, lds, s) : bsc_launch_es1<I, Q8, false>(a, nblocks, nw, lds, s);
+typedef int (*BscLaunchFn)(const BscLaunch&, int, int, size_t, hipStream_t, bool, bool);
+template <int... I>
+constexpr std::array<BscLaunchFn, sizeof...(I)> bsc_launch_table(std::integer_sequence<int, I...>) {
+    return {&bsc_launch<I>...};
 }
 
 }  // namespace bs
@@ -1163,85 +1148,50 @@ int bsc_debug_bounds(const DevGraph& g, int mode, float clip, int T, int flags, 
     return 1;
 }
 
-bool bsc_q8_ok(const DevGraph& g, int mode, bool ucn, float clip, int T, bool has_short) {
-    const BscPlan p = bsc_plan(g, mode, ucn, false, clip, T);
+// ---- requests (ldpc_fused.h); early stop: DESIGN 3.7 -------------------------------------------
+static BscPlan bsc_plan(const DevGraph& g, const BsReq& r) {
+    return bsc_plan(g, r.mode, r.ucn, r.per_edge_w, r.clip, r.T, r.es);
+}
+
+bool bsc_supported(const DevGraph& g, const BsReq& r) { return bsc_plan(g, r).ok; }
+
+bool bsc_q8_ok(const DevGraph& g, const BsReq& r, bool has_short) {
+    const BscPlan p = bsc_plan(g, r);
     // (the in-prologue channel's tables borrow the SGN region at LDS byte 0)
     return p.ok && (!has_short || p.cu > 0.f) && q8_tab_fits(p);
 }
 
-bool bsc_supported(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T) {
-    return bsc_plan(g, mode, ucn, per_edge_w, clip, T).ok;
-}
-
-const char* bsc_kernel_name(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T) {
+const char* bsc_kernel_name(const DevGraph& g, const BsReq& r) {
     static thread_local char buf[64];
-    const BscPlan p = bsc_plan(g, mode, ucn, per_edge_w, clip, T);
+    const BscPlan p = bsc_plan(g, r);
     if (!p.ok) return "";
     const BscInst& k = kBscInst[p.inst];
-    snprintf(buf, sizeof(buf), "bsc[p32,w%d,d%d,v%d/%d,l%d%s,x%d/%d]", p.nw, k.D, k.DVH, k.DVL, k.LPC,
-             k.MIX ? "/2" : "", k.VPL, k.CPL);
+    snprintf(buf, sizeof(buf), "bsc[p32,w%d,d%d,v%d/%d,l%d%s,x%d/%d%s]", p.nw, k.D, k.DVH, k.DVL, k.LPC,
+             k.MIX ? "/2" : "", k.VPL, k.CPL, r.es ? ",es" : "");
     return buf;
 }
 
-// ---- early stop ---------------------------------------------------------------
-bool bsc_es_supported(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T) {
-    return bsc_plan(g, mode, ucn, per_edge_w, clip, T, true).ok;
-}
-bool bsc_es_q8_ok(const DevGraph& g, int mode, bool ucn, float clip, int T, bool has_short) {
-    const BscPlan p = bsc_plan(g, mode, ucn, false, clip, T, true);
-    return p.ok && (!has_short || p.cu > 0.f) && q8_tab_fits(p);
-}
-const char* bsc_es_kernel_name(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T) {
-    static thread_local char buf[64];
-    const BscPlan p = bsc_plan(g, mode, ucn, per_edge_w, clip, T, true);
-    if (!p.ok) return "";
-    const BscInst& k = kBscInst[p.inst];
-    snprintf(buf, sizeof(buf), "bsc[p32,w%d,d%d,v%d/%d,l%d%s,x%d/%d,es]", p.nw, k.D, k.DVH, k.DVL, k.LPC,
-             k.MIX ? "/2" : "", k.VPL, k.CPL);
-    return buf;
-}
-
-// one launch of plan p; es: the early-stop outputs (an early-stop plan), else null
-struct BscEsOut { uint8_t* n_iter; int64_t* iter_hist; uint32_t* hdw; };
-static int bsc_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const BscPlan& p, const float* llr, int mode,
-                   int64_t* counters, uint8_t* flags, uint32_t* bad, uint32_t* hdx, bool word, const BscEsOut* es,
-                   hipStream_t s) {
+// one launch of plan p (an early-stop plan for an early-stop request)
+static int bsc_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const BscPlan& p, const float* llr,
+                   const BsReq& r, const BsOut& o, hipStream_t s) {
     // (the graph tables do not depend on the mode: both kinds of decode share them)
     int st = bsc_tables(g, p, ws, s);
     if (st != LDPC_OK) return st;
     const BscInst& k = kBscInst[p.inst];
-    const float step = bs_step(mode);
+    const float step = bs_step(r.mode);
     uint32_t *alut = nullptr, *blut = nullptr;
-    st = bs_make_tables(b, g, p.arows, p.arows, p.bcols, step, bs_qmax(mode), p.cu, false, ws, &alut, &blut, s);
+    st = bs_make_tables(b, g, p.arows, p.arows, p.bcols, step, bs_qmax(r.mode), p.cu, false, ws, &alut, &blut, s);
     if (st != LDPC_OK) return st;
     const uint32_t* gt = reinterpret_cast<const uint32_t*>(ws.bs_graph);
     const int VNW = k.DVH + 1;
-    // (BscArgs, and the early-stop builds' additions: their launch reads them, every other launch
-    // takes the BscArgs base alone)
-    BscArgsEw a{};
-    if (es) {
-        a.n_iter = es->n_iter;
-        a.iter_hist = es->iter_hist;
-        a.off_u = p.off_u;
-        a.hdw = es->hdw;
-    }
-    const bool q8 = b.q8 != nullptr;
+    BscLaunch a{};
+    a.n_iter = o.n_iter;
+    a.iter_hist = o.iter_hist;
+    a.off_u = p.off_u;
+    a.hdw = o.hdw;
+    a.word = o.word ? 1 : 0;
     a.llr = llr;
-    if (b.q8) {                          // the in-prologue channel (ldpc_decode_awgn)
-        const AwgnParams& g8 = *reinterpret_cast<const AwgnParams*>(b.gen8);
-        a.gen.tab = b.q8;
-        a.gen.k0 = g8.k0;
-        a.gen.k1 = g8.k1;
-        a.gen.offset = g8.offset;
-        a.gen.nb = g8.nb;
-        a.gen.kmin = g8.kmin;
-        a.gen.ps = g8.ps;
-        a.gen.pe = g8.pe;
-        a.gen.ss = g8.ss;
-        a.gen.se = g8.se;
-        a.gen.lds = q8_tab_lds(p);
-    }
-
+    a.gen = bs_gen(b, q8_tab_lds(p));    // the in-prologue channel (ldpc_decode_awgn)
     a.B = b.B;
     a.n_vars = g.n_vars;
     a.n_checks = g.n_checks;
@@ -1251,7 +1201,7 @@ static int bsc_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const B
     a.z = g.z;
     a.inv = 1.0f / step;
     a.cu = p.cu;
-    a.qmax = bs_qmax(mode);
+    a.qmax = bs_qmax(r.mode);
     a.beta_id = g.w_beta_one ? 1 : 0;
     a.row_ptr = g.row_ptr;
     a.vn_tab = gt;
@@ -1262,16 +1212,16 @@ static int bsc_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const B
     a.cn_var = reinterpret_cast<const uint32_t*>(a.cn_chunk + (size_t)p.nw * k.CPL);
     a.cn_lane = reinterpret_cast<const int32_t*>(a.cn_var + (size_t)p.cn_lanes * ((((k.D + k.LPC - 1) / k.LPC) + 1) / 2));
     // (LDPC_BS_STAGGER still applies; C5: no gain.  Early stop: none, the packs end at different times)
-    if (!es) bs_stagger(false, &a.stagger, &a.stagger_n);
+    if (!r.es) bs_stagger(false, &a.stagger, &a.stagger_n);
     a.alut = alut;
     a.blut = blut;
     a.arows = p.arows;
     a.bcols = p.bcols;
-    a.counters = counters;
-    a.flags = flags;
-    a.bad = bad;
-    a.iter_wrong = es ? nullptr : b.iter_wrong;
-    a.hdx = hdx;
+    a.counters = o.counters;
+    a.flags = o.flags;
+    a.bad = o.bad;
+    a.iter_wrong = r.es ? nullptr : b.iter_wrong;
+    a.hdx = o.hdx;
     a.off_a = p.off_a;
     a.off_rec = p.off_rec;
     a.off_tv = p.off_tv;
@@ -1279,47 +1229,17 @@ static int bsc_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const B
     a.off_alut = p.off_alut;
     a.off_blut = p.off_blut;
     const int nblocks = (int)((b.B + PACK - 1) / PACK);
-    if (es) {
-        if (hdx || !p.es || !a.beta_id || a.bcols != 1) return LDPC_ERR_UNSUPPORTED;
-        switch (p.inst) {
-            case 3: return q8 ? bsc_launch_es<3, true>(a, nblocks, p.nw, p.lds, s) : bsc_launch_es<3, false>(a, nblocks, p.nw, p.lds, s);
-            case 4: return q8 ? bsc_launch_es<4, true>(a, nblocks, p.nw, p.lds, s) : bsc_launch_es<4, false>(a, nblocks, p.nw, p.lds, s);
-            default: return LDPC_ERR_UNSUPPORTED;
-        }
-    }
-    // (an export launch: BscArgsXp, the word mode's switch after the BscArgs base)
-    BscArgsXp ax{};
-    if (hdx) {
-        static_cast<BscArgs&>(ax) = a;
-        ax.word = word ? 1 : 0;
-    }
-    switch (p.inst) {
-        case 1: return hdx ? bsc_launch<1, true>(ax, nblocks, p.nw, p.lds, s, q8) : bsc_launch<1, false>(a, nblocks, p.nw, p.lds, s, q8);
-        case 2: return hdx ? bsc_launch<2, true>(ax, nblocks, p.nw, p.lds, s, q8) : bsc_launch<2, false>(a, nblocks, p.nw, p.lds, s, q8);
-        case 3: return hdx ? bsc_launch<3, true>(ax, nblocks, p.nw, p.lds, s, q8) : bsc_launch<3, false>(a, nblocks, p.nw, p.lds, s, q8);
-        case 4: return hdx ? bsc_launch<4, true>(ax, nblocks, p.nw, p.lds, s, q8) : bsc_launch<4, false>(a, nblocks, p.nw, p.lds, s, q8);
-        default: return hdx ? bsc_launch<0, true>(ax, nblocks, p.nw, p.lds, s, q8) : bsc_launch<0, false>(a, nblocks, p.nw, p.lds, s, q8);
-    }
+    static constexpr auto kLaunch = bsc_launch_table(std::make_integer_sequence<int, kBscNInst>{});
+    return kLaunch[p.inst](a, nblocks, p.nw, p.lds, s, b.q8 != nullptr, r.es);
 }
 
-int bsc_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode,
-               bool ucn, int64_t* counters, uint8_t* flags, uint32_t* bad, uint32_t* hdx, bool word, hipStream_t s) {
-    const BscPlan p = bsc_plan(g, mode, ucn, false, b.clip, b.T);
+// (bs_decode falls through to it; LDPC_ERR_UNSUPPORTED with nothing launched when no build serves
+// the request)
+int bsc_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, const BsReq& r,
+               const BsOut& o, hipStream_t s) {
+    const BscPlan p = bsc_plan(g, r);
     if (!p.ok) return LDPC_ERR_UNSUPPORTED;
-    return bsc_run(g, b, ws, p, llr, mode, counters, flags, bad, hdx, word, nullptr, s);
-}
-
-// the early-stop decode (as bs_decode_es, which falls through to it): LDPC_ERR_UNSUPPORTED with
-// nothing launched when no early-stop build serves the request
-int bsc_decode_es(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode, bool ucn,
-                  int64_t* counters, uint8_t* flags, uint32_t* bad, uint8_t* n_iter, int64_t* iter_hist,
-                  uint32_t* hdw, hipStream_t s) {
-    const BscPlan p = bsc_plan(g, mode, ucn, false, b.clip, b.T, true);
-    if (!p.ok) return LDPC_ERR_UNSUPPORTED;
-    if (b.q8 && !bsc_es_q8_ok(g, mode, ucn, b.clip, b.T, reinterpret_cast<const AwgnParams*>(b.gen8)->ss > 0))
-        return LDPC_ERR_UNSUPPORTED;
-    const BscEsOut es{n_iter, iter_hist, hdw};
-    return bsc_run(g, b, ws, p, llr, mode, counters, flags, bad, nullptr, false, &es, s);
+    return bsc_run(g, b, ws, p, llr, r, o, s);
 }
 
 }  // namespace ldpc

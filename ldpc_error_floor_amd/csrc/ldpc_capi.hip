@@ -2,6 +2,7 @@
 // dispatch, and the small compat kernels (output export, FER/BER counter finalisation).
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <vector>
 
@@ -418,12 +419,18 @@ int ldpc_decode(ldpc_ctx* c, const float* llr_dev, int64_t B, const ldpc_decode_
     return decode_impl(c, llr_dev, B, p, o, stream, nullptr);
 }
 
+// LDPC_AWGN_Q8=0: the bit-sliced kernels never generate the channel in their prologue (an A/B and
+// test switch, read once)
+static bool awgn_q8_on() {
+    static const bool on = [] { const char* e = getenv("LDPC_AWGN_Q8"); return !(e && atoi(e) == 0); }();
+    return on;
+}
+
 // ldpc_decode_awgn's byte channel in the bit-sliced kernels' prologue (their Q8 build) serves a
-// counters-only decode with these parameters (LDPC_AWGN_Q8=0: never, an A/B and test switch)
+// counters-only decode with these parameters
 static bool q8_serves(const ldpc_ctx* c, const ldpc_decode_params* p, bool has_short) {
-    static const bool q8_on = [] { const char* e = getenv("LDPC_AWGN_Q8"); return !(e && atoi(e) == 0); }();
     const ldpc_graph* g = c->g;
-    return q8_on && p->decoding_type == LDPC_DEC_QMS && p->kernel != LDPC_KERNEL_FLOOD &&
+    return awgn_q8_on() && p->decoding_type == LDPC_DEC_QMS && p->kernel != LDPC_KERNEL_FLOOD &&
            fused_q8_ok(g->dev, mode_of(p->decoding_type, p->q_bit), p->T, p->clip_llr,
                        g->d_alpha_ucn != nullptr, g->per_edge_w != 0, has_short);
 }
@@ -467,15 +474,33 @@ static int ensure_llr_scratch(ldpc_ctx* c) {
     const int64_t n = c->B_max * (int64_t)g->h.N * g->h.z;
     if (c->llr_scratch_n >= n) return LDPC_OK;
     DeviceGuard dg(g->device);
-    if (c->llr_scratch) (void)hipFree(c->llr_scratch);
-    c->llr_scratch = nullptr;
-    c->llr_scratch_n = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&c->llr_scratch), (size_t)n * sizeof(float)) != hipSuccess) {
-        (void)hipGetLastError();
-        return LDPC_ERR_OOM;
-    }
-    c->llr_scratch_n = n;
-    return LDPC_OK;
+    return dev_grow(c->llr_scratch, c->llr_scratch_n, (size_t)n);
+}
+
+// the buffers and scalars every decode starts from (counting on)
+static Bufs make_bufs(const ldpc_ctx* c, int64_t B, const ldpc_decode_params* p) {
+    const ldpc_graph* g = c->g;
+    Bufs b{};
+    b.B = B;
+    b.ntiles = (int)((B + TILE - 1) / TILE);
+    b.T = p->T;
+    b.n_vars = g->h.N * g->h.z;
+    b.target_bits = p->target_bits;
+    b.clip = p->clip_llr;
+    b.alpha = g->d_alpha;
+    b.alpha_ucn = g->d_alpha_ucn;
+    b.beta = g->d_beta;
+    b.count = 1;
+    return b;
+}
+
+// ldpc_ctx_last_kernel's name of the decode just served: the kernel's, with ",word" inside its
+// brackets for the word modes, and "+gen" for a channel generated inside the decoding kernel (the
+// bit-sliced Q8 build or the v5 prologue), so a caller can tell it from a decode of LLRs in HBM
+static void set_last_kernel(ldpc_ctx* c, const char* kernel, bool word, bool gen) {
+    const size_t n = std::strlen(kernel);
+    std::snprintf(c->last_kernel, sizeof(c->last_kernel), "%.*s%s%s", (int)(word && n ? n - 1 : n), kernel,
+                  word ? ",word]" : "", gen ? "+gen" : "");
 }
 
 int ldpc_awgn_in_kernel(const ldpc_ctx* c, const ldpc_decode_params* p, int32_t has_short, int32_t app) {
@@ -495,33 +520,33 @@ int ldpc_awgn_in_kernel(const ldpc_ctx* c, const ldpc_decode_params* p, int32_t 
                          app != 0) ? 1 : 0;
 }
 
-int ldpc_decode_awgn(ldpc_ctx* c, int64_t B, const ldpc_decode_params* p,
-                     const ldpc_channel_params* ch, const ldpc_decode_outputs* o, void* stream) {
-    if (!c || !p || !ch || !(ch->sigma > 0.0) || ch->offset < 0) return LDPC_ERR_ARG;
-    if (B <= 0 || B > c->B_max) return LDPC_ERR_STATE;
-    const AwgnParams a = make_awgn(ch->sigma, ch->seed, ch->offset, p->decoding_type, p->q_bit,
-                                   ch->punct_start, ch->punct_end, ch->short_start, ch->short_end,
-                                   p->clip_llr);
-    int st = decode_impl(c, nullptr, B, p, o, stream, &a);
-    if (st != LDPC_ERR_UNSUPPORTED) return st;
+static AwgnParams awgn_of(const ldpc_channel_params* ch, const ldpc_decode_params* p) {
+    return make_awgn(ch->sigma, ch->seed, ch->offset, p->decoding_type, p->q_bit, ch->punct_start,
+                     ch->punct_end, ch->short_start, ch->short_end, p->clip_llr);
+}
+
+// A decode of B codewords of the AWGN channel `ch`; dec(llr, q8, gen8) is the decode.  in_prologue:
+// the bit-sliced kernels generate the channel in their prologue (SURVEY 8 f rank 1) -- the LLRs
+// never touch HBM (oracle/philox_oracle.awgn_q8); the sampler's tables (8.25 KB) are uploaded when
+// the channel parameters change, and gen_done is recorded behind the decode that reads them.
+// Otherwise, or when that decode answers LDPC_ERR_UNSUPPORTED, the kernel reads its LLRs: the
+// channel kernel writes them into the context's buffer first.
+typedef std::function<int(const float* llr, const uint32_t* q8, const AwgnParams* gen8)> AwgnDecode;
+static int decode_awgn_with(ldpc_ctx* c, int64_t B, const ldpc_decode_params* p, const ldpc_channel_params* ch,
+                            const AwgnParams& a, bool in_prologue, void* stream, const AwgnDecode& dec) {
     ldpc_graph* g = c->g;
-    // counters-only QMS decodes the bit-sliced kernels serve: the channel generated in their
-    // prologue (SURVEY 8 f rank 1) -- the LLRs never touch HBM (oracle/philox_oracle.awgn_q8); the
-    // sampler's tables (8.25 KB) are uploaded when the channel parameters change
-    // (counters / flags / iter_wrong only: hard-bit and syndrome exports take the export build,
-    // which reads its LLRs)
-    if ((!o || (!o->app_all && !o->hard_bits && !o->synd_bits)) && q8_serves(c, p, ch->short_start > 0)) {
+    int st;
+    if (in_prologue) {
         DeviceGuard dg(g->device);
         st = ensure_gen_tab(c, a, stream);
         if (st != LDPC_OK) return st;
-        st = decode_impl(c, nullptr, B, p, o, stream, nullptr, c->gen_tab, &a);
+        st = dec(nullptr, c->gen_tab, &a);
         if (st == LDPC_OK) {
             if (hipEventRecord(c->gen_done, reinterpret_cast<hipStream_t>(stream)) != hipSuccess) return LDPC_ERR_HIP;
             c->gen_pending = true;
         }
         if (st != LDPC_ERR_UNSUPPORTED) return st;
     }
-    // this kernel reads its LLRs: generate them into the context's buffer, then decode
     st = ensure_llr_scratch(c);
     if (st != LDPC_OK) return st;
     {
@@ -531,7 +556,23 @@ int ldpc_decode_awgn(ldpc_ctx* c, int64_t B, const ldpc_decode_params* p,
                                ch->short_start, ch->short_end, p->clip_llr, stream);
     }
     if (st != LDPC_OK) return st;
-    return decode_impl(c, c->llr_scratch, B, p, o, stream, nullptr);
+    return dec(c->llr_scratch, nullptr, nullptr);
+}
+
+int ldpc_decode_awgn(ldpc_ctx* c, int64_t B, const ldpc_decode_params* p,
+                     const ldpc_channel_params* ch, const ldpc_decode_outputs* o, void* stream) {
+    if (!c || !p || !ch || !(ch->sigma > 0.0) || ch->offset < 0) return LDPC_ERR_ARG;
+    if (B <= 0 || B > c->B_max) return LDPC_ERR_STATE;
+    const AwgnParams a = awgn_of(ch, p);
+    const int st = decode_impl(c, nullptr, B, p, o, stream, &a);      // the v5 kernel's prologue channel
+    if (st != LDPC_ERR_UNSUPPORTED) return st;
+    // counters-only QMS decodes the bit-sliced kernels serve: their in-prologue channel
+    // (counters / flags / iter_wrong only: hard-bit and syndrome exports take the export build,
+    // which reads its LLRs)
+    const bool q8 = (!o || (!o->app_all && !o->hard_bits && !o->synd_bits)) && q8_serves(c, p, ch->short_start > 0);
+    return decode_awgn_with(c, B, p, ch, a, q8, stream, [&](const float* llr, const uint32_t* tab, const AwgnParams* gen8) {
+        return decode_impl(c, llr, B, p, o, stream, nullptr, tab, gen8);
+    });
 }
 
 int ldpc_kernel_info(const ldpc_ctx* c, const ldpc_decode_params* p, int64_t* bytes_per_cw,
@@ -617,16 +658,7 @@ static int decode_impl(ldpc_ctx* c, const float* llr_dev, int64_t B, const ldpc_
 
     const int ntiles = (int)((B + TILE - 1) / TILE);
     const bool count = out.counters || out.frame_flags || out.iter_wrong;
-    Bufs b{};
-    b.B = B;
-    b.ntiles = ntiles;
-    b.T = p->T;
-    b.n_vars = g->h.N * g->h.z;
-    b.target_bits = p->target_bits;
-    b.clip = p->clip_llr;
-    b.alpha = g->d_alpha;
-    b.alpha_ucn = g->d_alpha_ucn;
-    b.beta = g->d_beta;
+    Bufs b = make_bufs(c, B, p);
     b.app_out = out.app_all;
     b.count = count ? 1 : 0;
     b.wrong = c->wrong;
@@ -669,10 +701,7 @@ static int decode_impl(ldpc_ctx* c, const float* llr_dev, int64_t B, const ldpc_
     const char* served = kern == LDPC_KERNEL_FLOOD ? "flood"
                          : fl ? ffl_kernel_name(g->dev, mode, ucn, g->per_edge_w != 0)
                               : c->fused.last_kernel;
-    // (a channel generated inside the decoding kernel -- the bit-sliced Q8 build or the v5
-    // prologue -- is marked "+gen", so a caller can tell it from a decode of LLRs in HBM)
-    std::snprintf(c->last_kernel, sizeof(c->last_kernel), "%s%s", served,
-                  (q8 || (gen && kern == LDPC_KERNEL_FUSED)) ? "+gen" : "");
+    set_last_kernel(c, served, false, q8 || (gen && kern == LDPC_KERNEL_FUSED));
 
     if (count && kern == LDPC_KERNEL_FLOOD) {
         hipLaunchKernelGGL(k_finalize, dim3(std::min(1024, (ntiles + 255) / 256)), dim3(256), 0, s, b,
@@ -712,123 +741,94 @@ static int decode_impl(ldpc_ctx* c, const float* llr_dev, int64_t B, const ldpc_
     return hipGetLastError() == hipSuccess ? LDPC_OK : LDPC_ERR_HIP;
 }
 
-// ---- early stop (include/ldpc_nms.h) ------------------------------------------
-// the request's mode when an early-stop instance serves it, LDPC_ERR_UNSUPPORTED when none does,
-// or the status of a bad request (no device call)
-static int es_request(const ldpc_ctx* c, int64_t B, const ldpc_decode_params* p, int* mode) {
+// ---- the bit-sliced modes (include/ldpc_nms.h): early stop, the decoded word (3.8),
+// early stop with the word (3.9) ---------------------------------------------------------------
+// the request (*r) when the bit-sliced kernels decode it in this mode, LDPC_ERR_UNSUPPORTED when
+// they do not, or the status of a bad request (no device call)
+static int bs_request(const ldpc_ctx* c, int64_t B, const ldpc_decode_params* p, bool es, BsReq* r) {
     const ldpc_graph* g = c->g;
     if (!g->d_alpha || !g->d_beta) return LDPC_ERR_STATE;
-    const int chk = host::check_decode(g->h, B, c->B_max, c->T_max, g->T_w, p, mode);
+    int mode = -1;
+    const int chk = host::check_decode(g->h, B, c->B_max, c->T_max, g->T_w, p, &mode);
     if (chk != LDPC_OK) return chk;
     if (p->kernel != LDPC_KERNEL_AUTO && p->kernel != LDPC_KERNEL_FUSED)
         return p->kernel == LDPC_KERNEL_FLOOD ? LDPC_ERR_UNSUPPORTED : LDPC_ERR_ARG;
-    if (p->decoding_type != LDPC_DEC_QMS || g->per_edge_w ||
-        !bs_es_supported(g->dev, *mode, g->d_alpha_ucn != nullptr, false, p->clip_llr, p->T))
+    *r = BsReq{mode, g->d_alpha_ucn != nullptr, false, p->clip_llr, p->T, es};
+    if (p->decoding_type != LDPC_DEC_QMS || g->per_edge_w || !fused_bs_supported(g->dev, *r))
         return LDPC_ERR_UNSUPPORTED;
     return LDPC_OK;
 }
 
-int ldpc_es_supported(const ldpc_ctx* c, const ldpc_decode_params* p) {
+static int bs_request_supported(const ldpc_ctx* c, const ldpc_decode_params* p, bool es) {
     if (!c || !p) return LDPC_ERR_ARG;
-    int mode = -1;
-    const int st = es_request(c, 1, p, &mode);
+    BsReq r{};
+    const int st = bs_request(c, 1, p, es, &r);
     return st == LDPC_OK ? 1 : st == LDPC_ERR_UNSUPPORTED ? 0 : st;
 }
+int ldpc_es_supported(const ldpc_ctx* c, const ldpc_decode_params* p) { return bs_request_supported(c, p, true); }
+int ldpc_es_word_supported(const ldpc_ctx* c, const ldpc_decode_params* p) { return ldpc_es_supported(c, p); }
+int ldpc_word_supported(const ldpc_ctx* c, const ldpc_decode_params* p) { return bs_request_supported(c, p, false); }
 
-// (what either early-stop entry point asks for; hard_stop: the decoded word too)
-struct EsOuts {
+// (what the entry points of these modes ask for; rows: hard_last / hard_stop, the decoded word)
+struct BsOuts {
     int64_t* counters;
     uint8_t *frame_flags, *n_iter;
     int64_t* iter_hist;
-    uint32_t* hard_stop;
+    uint32_t* rows;
     uint8_t* word_flags;
 };
-static EsOuts es_outs(const ldpc_es_outputs* o) {
-    return EsOuts{o->counters, o->frame_flags, o->n_iter, o->iter_hist, nullptr, nullptr};
+static BsOuts bs_outs(const ldpc_es_outputs* o) {
+    return BsOuts{o->counters, o->frame_flags, o->n_iter, o->iter_hist, nullptr, nullptr};
 }
-static EsOuts es_outs(const ldpc_es_word_outputs* o) {
-    return EsOuts{o->counters, o->frame_flags, o->n_iter, o->iter_hist, o->hard_stop, o->word_flags};
+static BsOuts bs_outs(const ldpc_es_word_outputs* o) {
+    return BsOuts{o->counters, o->frame_flags, o->n_iter, o->iter_hist, o->hard_stop, o->word_flags};
+}
+static BsOuts bs_outs(const ldpc_word_outputs* o) {
+    return BsOuts{o->counters, o->frame_flags, nullptr, nullptr, o->hard_last, o->word_flags};
 }
 
-static int decode_es_impl(ldpc_ctx* c, const float* llr_dev, int64_t B, const ldpc_decode_params* p,
-                          const EsOuts& o, void* stream, const uint32_t* q8, const AwgnParams* gen8) {
-    int mode = -1;
-    const int rq = es_request(c, B, p, &mode);
+static int decode_bs_impl(ldpc_ctx* c, const float* llr_dev, int64_t B, const ldpc_decode_params* p, bool es,
+                          const BsOuts& o, void* stream, const uint32_t* q8, const AwgnParams* gen8) {
+    BsReq r{};
+    const int rq = bs_request(c, B, p, es, &r);
     if (rq != LDPC_OK) return rq;
     ldpc_graph* g = c->g;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     DeviceGuard dg(g->device);
-    const bool ucn = g->d_alpha_ucn != nullptr;
-    Bufs b{};
-    b.B = B;
-    b.ntiles = (int)((B + TILE - 1) / TILE);
-    b.T = p->T;
-    b.n_vars = g->h.N * g->h.z;
-    b.target_bits = p->target_bits;
-    b.clip = p->clip_llr;
-    b.alpha = g->d_alpha;
-    b.alpha_ucn = g->d_alpha_ucn;
-    b.beta = g->d_beta;
-    b.count = 1;
+    Bufs b = make_bufs(c, B, p);
     b.q8 = q8;
     b.gen8 = gen8;
-    const int st = o.hard_stop
-        ? fused_decode_es_word(g->dev, b, c->fused, llr_dev, mode, ucn, c->B_max, c->ntiles_max, o.counters,
-                               o.frame_flags, o.n_iter, o.iter_hist, o.hard_stop, o.word_flags, s)
-        : bs_decode_es(g->dev, b, c->fused, llr_dev, mode, ucn, c->ntiles_max, o.counters, o.frame_flags,
-                       o.n_iter, o.iter_hist, nullptr, s);
+    BsOut bo{};
+    bo.counters = o.counters;
+    bo.flags = o.frame_flags;
+    bo.n_iter = o.n_iter;
+    bo.iter_hist = o.iter_hist;
+    const int st = fused_decode_bs(g->dev, b, c->fused, llr_dev, r, c->B_max, c->ntiles_max, bo, o.rows,
+                                   o.word_flags, s);
     if (st != LDPC_OK) return st;
-    const char* nm = bs_es_kernel_name(g->dev, mode, ucn, false, p->clip_llr, p->T);
-    if (o.hard_stop) {                   // the early-stop name with ",word" inside the brackets
-        const size_t n = std::strlen(nm);
-        std::snprintf(c->last_kernel, sizeof(c->last_kernel), "%.*s,word]%s", (int)(n ? n - 1 : 0), nm,
-                      q8 ? "+gen" : "");
-    } else {
-        std::snprintf(c->last_kernel, sizeof(c->last_kernel), "%s%s", nm, q8 ? "+gen" : "");
-    }
+    set_last_kernel(c, bs_kernel_name(g->dev, r), o.rows != nullptr, q8 != nullptr);
     return hipGetLastError() == hipSuccess ? LDPC_OK : LDPC_ERR_HIP;
+}
+
+// (the early-stop decode of an AWGN channel.  LDPC_ERR_UNSUPPORTED from the in-prologue decode
+// would go on to the channel kernel, as ldpc_decode_awgn's does, but cannot occur: bs_request and
+// bs_q8_ok have passed, and they are all that fused_decode_bs and the launch refuse)
+static int decode_awgn_es_impl(ldpc_ctx* c, int64_t B, const ldpc_decode_params* p, const ldpc_channel_params* ch,
+                               const BsOuts& o, void* stream) {
+    BsReq r{};
+    const int st = bs_request(c, B, p, true, &r);
+    if (st != LDPC_OK) return st;
+    const bool q8 = awgn_q8_on() && bs_q8_ok(c->g->dev, r, ch->short_start > 0);
+    return decode_awgn_with(c, B, p, ch, awgn_of(ch, p), q8, stream,
+                            [&](const float* llr, const uint32_t* tab, const AwgnParams* gen8) {
+                                return decode_bs_impl(c, llr, B, p, true, o, stream, tab, gen8);
+                            });
 }
 
 int ldpc_decode_es(ldpc_ctx* c, const float* llr_dev, int64_t B, const ldpc_decode_params* p,
                    const ldpc_es_outputs* o, void* stream) {
     if (!c || !llr_dev || !p || !o || o->size != (int32_t)sizeof(ldpc_es_outputs)) return LDPC_ERR_ARG;
-    return decode_es_impl(c, llr_dev, B, p, es_outs(o), stream, nullptr, nullptr);
-}
-
-static int decode_awgn_es_impl(ldpc_ctx* c, int64_t B, const ldpc_decode_params* p, const ldpc_channel_params* ch,
-                               const EsOuts& o, void* stream) {
-    int mode = -1;
-    int st = es_request(c, B, p, &mode);
-    if (st != LDPC_OK) return st;
-    ldpc_graph* g = c->g;
-    const AwgnParams a = make_awgn(ch->sigma, ch->seed, ch->offset, p->decoding_type, p->q_bit,
-                                   ch->punct_start, ch->punct_end, ch->short_start, ch->short_end,
-                                   p->clip_llr);
-    static const bool q8_on = [] { const char* e = getenv("LDPC_AWGN_Q8"); return !(e && atoi(e) == 0); }();
-    if (q8_on && bs_es_q8_ok(g->dev, mode, g->d_alpha_ucn != nullptr, p->clip_llr, p->T, ch->short_start > 0)) {
-        {
-            DeviceGuard dg(g->device);
-            st = ensure_gen_tab(c, a, stream);
-        }
-        if (st != LDPC_OK) return st;
-        st = decode_es_impl(c, nullptr, B, p, o, stream, c->gen_tab, &a);
-        if (st == LDPC_OK) {
-            if (hipEventRecord(c->gen_done, reinterpret_cast<hipStream_t>(stream)) != hipSuccess) return LDPC_ERR_HIP;
-            c->gen_pending = true;
-        }
-        return st;
-    }
-    // the channel kernel writes float LLRs into the context's buffer first
-    st = ensure_llr_scratch(c);
-    if (st != LDPC_OK) return st;
-    {
-        DeviceGuard dg(g->device);
-        st = ldpc_channel_awgn(c->llr_scratch, B, g->h.N * g->h.z, ch->sigma, ch->seed, ch->offset,
-                               p->decoding_type, p->q_bit, ch->punct_start, ch->punct_end,
-                               ch->short_start, ch->short_end, p->clip_llr, stream);
-    }
-    if (st != LDPC_OK) return st;
-    return decode_es_impl(c, c->llr_scratch, B, p, o, stream, nullptr, nullptr);
+    return decode_bs_impl(c, llr_dev, B, p, true, bs_outs(o), stream, nullptr, nullptr);
 }
 
 int ldpc_decode_awgn_es(ldpc_ctx* c, int64_t B, const ldpc_decode_params* p, const ldpc_channel_params* ch,
@@ -836,81 +836,30 @@ int ldpc_decode_awgn_es(ldpc_ctx* c, int64_t B, const ldpc_decode_params* p, con
     if (!c || !p || !ch || !o || o->size != (int32_t)sizeof(ldpc_es_outputs) || !(ch->sigma > 0.0) ||
         ch->offset < 0)
         return LDPC_ERR_ARG;
-    return decode_awgn_es_impl(c, B, p, ch, es_outs(o), stream);
+    return decode_awgn_es_impl(c, B, p, ch, bs_outs(o), stream);
 }
 
-// ---- early stop with the decoded word (include/ldpc_nms.h) ----------------------
 // (the outputs' size and the required row pointer are checked before the context is read)
 static_assert(sizeof(ldpc_es_word_outputs) == 64, "ldpc_es_word_outputs is part of ABI 3");
 int ldpc_decode_es_word(ldpc_ctx* c, const float* llr_dev, int64_t B, const ldpc_decode_params* p,
                         const ldpc_es_word_outputs* o, void* stream) {
     if (!o || o->size != (int32_t)sizeof(ldpc_es_word_outputs) || !o->hard_stop) return LDPC_ERR_ARG;
     if (!c || !llr_dev || !p) return LDPC_ERR_ARG;
-    return decode_es_impl(c, llr_dev, B, p, es_outs(o), stream, nullptr, nullptr);
+    return decode_bs_impl(c, llr_dev, B, p, true, bs_outs(o), stream, nullptr, nullptr);
 }
 
 int ldpc_decode_awgn_es_word(ldpc_ctx* c, int64_t B, const ldpc_decode_params* p, const ldpc_channel_params* ch,
                              const ldpc_es_word_outputs* o, void* stream) {
     if (!o || o->size != (int32_t)sizeof(ldpc_es_word_outputs) || !o->hard_stop) return LDPC_ERR_ARG;
     if (!c || !p || !ch || !(ch->sigma > 0.0) || ch->offset < 0) return LDPC_ERR_ARG;
-    return decode_awgn_es_impl(c, B, p, ch, es_outs(o), stream);
-}
-
-int ldpc_es_word_supported(const ldpc_ctx* c, const ldpc_decode_params* p) { return ldpc_es_supported(c, p); }
-
-// ---- decoded word (include/ldpc_nms.h) ------------------------------------------
-// the request's mode when the bit-sliced kernels decode it, LDPC_ERR_UNSUPPORTED when they do
-// not, or the status of a bad request (no device call)
-static int word_request(const ldpc_ctx* c, int64_t B, const ldpc_decode_params* p, int* mode) {
-    const ldpc_graph* g = c->g;
-    if (!g->d_alpha || !g->d_beta) return LDPC_ERR_STATE;
-    const int chk = host::check_decode(g->h, B, c->B_max, c->T_max, g->T_w, p, mode);
-    if (chk != LDPC_OK) return chk;
-    if (p->kernel != LDPC_KERNEL_AUTO && p->kernel != LDPC_KERNEL_FUSED)
-        return p->kernel == LDPC_KERNEL_FLOOD ? LDPC_ERR_UNSUPPORTED : LDPC_ERR_ARG;
-    if (p->decoding_type != LDPC_DEC_QMS || g->per_edge_w ||
-        !fused_word_supported(g->dev, *mode, p->T, p->clip_llr, g->d_alpha_ucn != nullptr, false))
-        return LDPC_ERR_UNSUPPORTED;
-    return LDPC_OK;
-}
-
-int ldpc_word_supported(const ldpc_ctx* c, const ldpc_decode_params* p) {
-    if (!c || !p) return LDPC_ERR_ARG;
-    int mode = -1;
-    const int st = word_request(c, 1, p, &mode);
-    return st == LDPC_OK ? 1 : st == LDPC_ERR_UNSUPPORTED ? 0 : st;
+    return decode_awgn_es_impl(c, B, p, ch, bs_outs(o), stream);
 }
 
 int ldpc_decode_word(ldpc_ctx* c, const float* llr_dev, int64_t B, const ldpc_decode_params* p,
                      const ldpc_word_outputs* o, void* stream) {
     if (!c || !llr_dev || !p || !o || o->size != (int32_t)sizeof(ldpc_word_outputs) || !o->hard_last)
         return LDPC_ERR_ARG;
-    int mode = -1;
-    const int rq = word_request(c, B, p, &mode);
-    if (rq != LDPC_OK) return rq;
-    ldpc_graph* g = c->g;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    DeviceGuard dg(g->device);
-    const bool ucn = g->d_alpha_ucn != nullptr;
-    Bufs b{};
-    b.B = B;
-    b.ntiles = (int)((B + TILE - 1) / TILE);
-    b.T = p->T;
-    b.n_vars = g->h.N * g->h.z;
-    b.target_bits = p->target_bits;
-    b.clip = p->clip_llr;
-    b.alpha = g->d_alpha;
-    b.alpha_ucn = g->d_alpha_ucn;
-    b.beta = g->d_beta;
-    b.count = 1;
-    const int st = fused_decode_word(g->dev, b, c->fused, llr_dev, mode, ucn, c->B_max, o->counters,
-                                     o->frame_flags, o->hard_last, o->word_flags, s);
-    if (st != LDPC_OK) return st;
-    // the kernel's usual name with ",word" inside the brackets
-    const char* nm = bs_kernel_name(g->dev, mode, ucn, false, p->clip_llr, p->T);
-    const size_t n = std::strlen(nm);
-    std::snprintf(c->last_kernel, sizeof(c->last_kernel), "%.*s,word]", (int)(n ? n - 1 : 0), nm);
-    return hipGetLastError() == hipSuccess ? LDPC_OK : LDPC_ERR_HIP;
+    return decode_bs_impl(c, llr_dev, B, p, false, bs_outs(o), stream, nullptr, nullptr);
 }
 
 int ldpc_ctx_last_kernel(const ldpc_ctx* c, char* name, int32_t name_len) {

@@ -33,6 +33,24 @@ struct FusedWorkspace {
     uint64_t key_gad[4] = {~0ull, 0, 0, 0}, key_qtab[4] = {~0ull, 0, 0, 0}, key_bslut[4] = {~0ull, 0, 0, 0};
 };
 
+// a grow-on-demand device buffer: at least n elements behind p afterwards (have: its size in
+// elements, of elem bytes each; the contents are not kept)
+template <class T, class N>
+int dev_grow(T*& p, N& have, size_t n, size_t elem) {
+    if ((size_t)have >= n) return LDPC_OK;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    have = 0;
+    if (hipMalloc(reinterpret_cast<void**>(&p), n * elem) != hipSuccess) {
+        (void)hipGetLastError();
+        return LDPC_ERR_OOM;
+    }
+    have = (N)n;
+    return LDPC_OK;
+}
+template <class T, class N>
+int dev_grow(T*& p, N& have, size_t n) { return dev_grow(p, have, n, sizeof(T)); }
+
 // fused v5 serves this request (QMS q in {5,-5,4,3}, clip_llr on the grid, a shape fits)
 bool fused_supported(const DevGraph& g, int mode, int T, float clip_llr);
 int64_t fused_bytes_per_cw(const DevGraph& g, int T);
@@ -59,76 +77,75 @@ int fused5_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const fl
                   int64_t* counters, uint8_t* flags, hipStream_t s, const uint32_t* only = nullptr);
 int fused5_cw(const DevGraph& g, int T);
 
-// bit-sliced (ldpc_bs.hip): 32 codewords per word, counters / flags only, QMS q = 5 / -5
-// (clip: clip_LLR, the LLR of shortened bits)
-// (T: the iteration count, whose per-iteration frame words take 4 T bytes of LDS)
-bool bs_supported(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T);
-const char* bs_kernel_name(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T);
-// hdx: null, or [T][packs][n_vars] u32: also store every iteration's hard decisions (bit r of
-// word (t, pack, v) = codeword 32 pack + r; the export build of the kernel).  word:
-// hdx is [packs][n_vars] and takes the last iteration's hard decisions alone
-int bs_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode,
-              bool ucn, int64_t* counters, uint8_t* flags, uint32_t* bad, uint32_t* hdx, bool word,
-              hipStream_t s);
-// the in-prologue channel (Bufs::q8 / gen8) serves this counters-only decode: the bit-sliced
-// kernel applies, has room for the sampler's tables in its slot region and, with shortened bits
-// in the channel, has the shortened-bit marker (a BIG instance)
-bool bs_q8_ok(const DevGraph& g, int mode, bool ucn, float clip, int T, bool has_short);
-bool bsc_q8_ok(const DevGraph& g, int mode, bool ucn, float clip, int T, bool has_short);
+// ---- the bit-sliced kernels: bsl (ldpc_bs.hip, 32 codewords per word, QMS q = 5 / -5 / 4 / 3)
+// and bsc (ldpc_bsc.hip, compressed check messages: the graphs whose per-edge slots exceed the LDS)
+// One request: the QMS grid, UCN weights set, per-edge CN weights (never served), clip_LLR (the
+// LLR of shortened bits), the iteration count (whose per-iteration frame words take 4 T bytes of
+// LDS), and es: syndrome-based early stop, which has kernel builds of its own.
+struct BsReq {
+    int mode;
+    bool ucn, per_edge_w;
+    float clip;
+    int T;
+    bool es;
+};
+// What one decode writes; null: off.
+struct BsOut {
+    int64_t* counters;         // [0..2]
+    uint8_t* flags;            // [B] frame flags
+    uint32_t* bad;             // [packs] 1: an LLR of the pack is off the quantizer grid (not decoded)
+    uint32_t* hdx;             // the export build: [T][packs][n_vars] every iteration's hard decisions
+                               // (bit r of word (t, pack, v) = codeword 32 pack + r)
+    bool word;                 // hdx is [packs][n_vars] and takes the last iteration's alone
+    uint8_t* n_iter;           // early stop: [B] iterations run (0: pack off the grid)
+    int64_t* iter_hist;        // early stop: [T] += codewords that ran t + 1 iterations
+    uint32_t* hdw;             // early stop: [packs][n_vars] each codeword's hard decisions at its
+                               // stop iteration (the EW builds)
+};
+// bs_*: bsl, or where no bsl plan serves the request, bsc (the fall-through).  An early-stop
+// request falls through only for a graph that no bsl plan at all serves (ldpc_bs.hip, bs_route).
+// q8_ok: the in-prologue channel (Bufs::q8 / gen8) serves the request's counters-only decode: the
+// kernel has room for the sampler's tables and, with shortened bits in the channel, the
+// shortened-bit marker; a caller checks it before it hands a decode b.q8.
+// kernel_name: "bsl[...]" / "bsc[...]", with ",es" inside the brackets for early stop; "" if unserved.
+bool bs_supported(const DevGraph& g, const BsReq& r);
+bool bs_q8_ok(const DevGraph& g, const BsReq& r, bool has_short);
+const char* bs_kernel_name(const DevGraph& g, const BsReq& r);
+bool bsc_supported(const DevGraph& g, const BsReq& r);
+bool bsc_q8_ok(const DevGraph& g, const BsReq& r, bool has_short);
+const char* bsc_kernel_name(const DevGraph& g, const BsReq& r);
+// the decode of b.B codewords (LLRs at llr, or the in-prologue channel b.q8 / b.gen8).  Packs with
+// an LLR off the grid are marked in o.bad (early stop: also flags 0x80, n_iter 0), not decoded.
+// LDPC_ERR_UNSUPPORTED: no build serves the request; nothing was launched.
+int bs_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, const BsReq& r,
+              const BsOut& o, hipStream_t s);
+int bsc_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, const BsReq& r,
+               const BsOut& o, hipStream_t s);
 // host-side bounds check of the bsc plan (test infrastructure, ldpc_debug_bs_bounds), and the
 // flags of that check (include/ldpc_nms_debug.h): no kernel or launch path reads them
 enum { LDPC_BOUNDS_PRE_GUARD = 1, LDPC_BOUNDS_BIG_TABLES = 2, LDPC_BOUNDS_ES = 4, LDPC_BOUNDS_ES_BSC = 8 };
 // (es: the graph's early-stop plan instead, LDPC_BOUNDS_ES_BSC)
 int bsc_debug_bounds(const DevGraph& g, int mode, float clip, int T, int flags, int& violations,
                      std::string& first, bool es = false);
-// early stop (ldpc_decode_es): the bit-sliced kernel's ES instances serve the request,
-// or, for a graph that no bsl plan serves, the compressed kernel's early-stop builds (bsc_*_es);
-// their decode (counters [0..2], frame flags, n_iter [B], iter_hist [T], each or null; b.q8 / gen8:
-// the in-prologue channel, when bs_es_q8_ok) and its kernel name ("bsl[...,es]" / "bsc[...,es]").
-// hdw: null, or [packs][n_vars] u32 that takes each codeword's hard decisions at its stop
-// iteration (the EW builds)
-bool bs_es_supported(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T);
-bool bs_es_q8_ok(const DevGraph& g, int mode, bool ucn, float clip, int T, bool has_short);
-const char* bs_es_kernel_name(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T);
-int bs_decode_es(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode, bool ucn,
-                 int ntiles_max, int64_t* counters, uint8_t* flags, uint8_t* n_iter, int64_t* iter_hist,
-                 uint32_t* hdw, hipStream_t s);
 // (fused_decode with it: the bit-sliced kernel or LDPC_ERR_UNSUPPORTED)
 bool fused_q8_ok(const DevGraph& g, int mode, int T, float clip, bool ucn, bool per_edge_w, bool has_short);
 // a decode with an in-kernel generator (Bufs::awgn) runs the v5 kernel's prologue channel
 bool fused_awgn_v5(const DevGraph& g, int mode, int T, float clip, bool ucn, bool per_edge_w, bool app);
-// compressed bit-sliced kernel (ldpc_bsc.hip): the graphs whose per-edge slots exceed the LDS
-bool bsc_supported(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T);
-const char* bsc_kernel_name(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T);
-int bsc_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode,
-               bool ucn, int64_t* counters, uint8_t* flags, uint32_t* bad, uint32_t* hdx, bool word,
-               hipStream_t s);
-// its early-stop builds: the beta = 1 build of the mixed-lane instances (bs_*_es fall through to
-// these where bs_decode falls through to bsc_decode); kernel name "bsc[...,es]"
-bool bsc_es_supported(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T);
-bool bsc_es_q8_ok(const DevGraph& g, int mode, bool ucn, float clip, int T, bool has_short);
-const char* bsc_es_kernel_name(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float clip, int T);
-int bsc_decode_es(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode, bool ucn,
-                  int64_t* counters, uint8_t* flags, uint32_t* bad, uint8_t* n_iter, int64_t* iter_hist,
-                  uint32_t* hdw, hipStream_t s);
-// the word mode (ldpc_decode_word): the request is one the bit-sliced kernels decode
-// (fused_decode would take bs_decode for its counters); the decode -- the export build storing
-// the last iteration's hard decisions alone into ws.hdw, no v5 fixup, then word_out --; and the
-// output kernel (ldpc_word.hip): hard_last [B][ceil(n_vars / 32)], word_flags [B] or null (bit 0:
-// syndrome nonzero), and, for the packs the decode marked off the grid (bad), zero rows and 0x80
-// in word_flags and frame_flags (or null)
+// The bit-sliced decodes without the v5 fixup: the word mode (ldpc_decode_word), early
+// stop (ldpc_decode_es; 3.7) and early stop with the word (ldpc_decode_es_word; 3.9).
+// fused_bs_supported: the request is one they decode: an early-stop request that bs_decode serves;
+// without early stop (the word mode), one fused_decode would take bs_decode for, of a graph with
+// at most WORD_MAX_VARS variables (word_out's bound).
+// fused_decode_bs: o takes counters, flags, n_iter and iter_hist; ws.bs_bad and, with rows, ws.hdw
+// are sized here.  rows: null, or [B][ceil(n_vars / 32)]: the export build (early stop: the EW
+// build) stores the last (the stop) iteration's hard decisions into ws.hdw, and the output kernel
+// word_out (ldpc_word.hip) writes the rows, word_flags [B] or null (bit 0: syndrome nonzero) and,
+// for the packs the decode marked off the grid, zero rows and 0x80 in word_flags and o.flags.
+// Nothing is allocated or launched for a request that is not served.
 constexpr int WORD_MAX_VARS = 4096;      // (the bit-sliced plans' bound: 4 variables on 1024 lanes)
-bool fused_word_supported(const DevGraph& g, int mode, int T, float clip, bool ucn, bool per_edge_w);
-int fused_decode_word(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode, bool ucn,
-                      int64_t B_max, int64_t* counters, uint8_t* flags, uint32_t* hard_last,
-                      uint8_t* word_flags, hipStream_t s);
-// the early-stop decode with the decoded word (ldpc_decode_es_word): bs_decode_es with
-// ws.hdw (sized as fused_decode_word's) taking each codeword's hard decisions at its stop
-// iteration, then word_out: hard_stop [B][ceil(n_vars / 32)], word_flags [B] or null.  Served
-// exactly where bs_decode_es is.
-int fused_decode_es_word(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode, bool ucn,
-                         int64_t B_max, int ntiles_max, int64_t* counters, uint8_t* flags, uint8_t* n_iter,
-                         int64_t* iter_hist, uint32_t* hard_stop, uint8_t* word_flags, hipStream_t s);
+bool fused_bs_supported(const DevGraph& g, const BsReq& r);
+int fused_decode_bs(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, const BsReq& r,
+                    int64_t B_max, int ntiles_max, BsOut o, uint32_t* rows, uint8_t* word_flags, hipStream_t s);
 int word_out(const DevGraph& g, const uint32_t* planes, const uint32_t* bad, int64_t B, uint32_t* hard_last,
              uint8_t* word_flags, uint8_t* frame_flags, hipStream_t s);
 void fused_free(FusedWorkspace& ws);

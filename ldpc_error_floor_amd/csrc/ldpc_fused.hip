@@ -39,6 +39,14 @@ int clip_units(int mode, float clip) {
     return (int)cu;
 }
 
+// ws.bs_bad: one word per pack of this call, and of the context's largest batch (8 packs per
+// 256-codeword tile) whatever this call's is.  Both bit-sliced kernels write a pack's off-grid
+// mark into it, the v5 fixup reads it as its `only` flags and word_out as the packs to blank, all
+// indexed by pack.
+int ensure_bs_bad(FusedWorkspace& ws, int64_t npk, int ntiles_max) {
+    return dev_grow(ws.bs_bad, ws.bs_bad_n, (size_t)std::max<int64_t>(npk, 8 * (int64_t)ntiles_max));
+}
+
 }  // namespace
 
 bool fused_supported(const DevGraph& g, int mode, int T, float clip_llr) {
@@ -49,28 +57,29 @@ bool fused_supported(const DevGraph& g, int mode, int T, float clip_llr) {
 }
 
 // counters-only decodes (throughput mode) run the bit-sliced kernel when it applies
-static bool use_bs(const DevGraph& g, int mode, int T, bool ucn, bool per_edge_w, float clip) {
-    const int cw = fused5_cw(g, T);
-    return cw > 0 && cw <= 32 && bs_supported(g, mode, ucn, per_edge_w, clip, T);
+static bool use_bs(const DevGraph& g, const BsReq& r) {
+    const int cw = fused5_cw(g, r.T);
+    return cw > 0 && cw <= 32 && bs_supported(g, r);
 }
 
 // the kernel a counters-only decode runs (the throughput / roofline report)
 const char* fused_kernel_name(const DevGraph& g, int mode, int T, float clip_llr, bool ucn,
                               bool per_edge_w) {
+    const BsReq r{mode, ucn, per_edge_w, clip_llr, T, false};
     if (!fused_supported(g, mode, T, clip_llr)) return "";
-    if (use_bs(g, mode, T, ucn, per_edge_w, clip_llr)) return bs_kernel_name(g, mode, ucn, per_edge_w, clip_llr, T);
+    if (use_bs(g, r)) return bs_kernel_name(g, r);
     return fused5_shape_name(g, T);
 }
 
 bool fused_q8_ok(const DevGraph& g, int mode, int T, float clip, bool ucn, bool per_edge_w, bool has_short) {
-    return fused_supported(g, mode, T, clip) && use_bs(g, mode, T, ucn, per_edge_w, clip) &&
-           bs_q8_ok(g, mode, ucn, clip, T, has_short);
+    const BsReq r{mode, ucn, per_edge_w, clip, T, false};
+    return fused_supported(g, mode, T, clip) && use_bs(g, r) && bs_q8_ok(g, r, has_short);
 }
 
 bool fused_awgn_v5(const DevGraph& g, int mode, int T, float clip, bool ucn, bool per_edge_w, bool app) {
     // fused_decode with a generator: the v5 prologue, except counters-only decodes the
     // bit-sliced kernels serve (UNSUPPORTED there: ldpc_decode_awgn then generates into HBM)
-    return fused_supported(g, mode, T, clip) && (app || !use_bs(g, mode, T, ucn, per_edge_w, clip));
+    return fused_supported(g, mode, T, clip) && (app || !use_bs(g, BsReq{mode, ucn, per_edge_w, clip, T, false}));
 }
 
 int64_t fused_bytes_per_cw(const DevGraph& g, int T) {
@@ -83,32 +92,23 @@ int fused_decode(const DevGraph& g, Bufs& b, FusedWorkspace& ws, const float* ll
                  bool ucn, bool want_bits, int ntiles_max, int T_max, int per_edge_w,
                  int64_t* counters, uint8_t* flags, hipStream_t s) {
     if (!fused_supported(g, mode, b.T, b.clip)) return LDPC_ERR_UNSUPPORTED;
+    const BsReq r{mode, ucn, per_edge_w != 0, b.clip, b.T, false};
     // counters-only decodes the bit-sliced kernel serves read their LLRs: with an in-kernel
     // channel requested, the caller (ldpc_decode_awgn) generates them into HBM first — the
     // channel kernel plus the bit-sliced decode beat the v5 kernel's in-prologue channel
-    if (b.awgn && !b.app_out && use_bs(g, mode, b.T, ucn, per_edge_w != 0, b.clip))
-        return LDPC_ERR_UNSUPPORTED;
+    if (b.awgn && !b.app_out && use_bs(g, r)) return LDPC_ERR_UNSUPPORTED;
     const float step = mode_step(mode);
     const int cu = clip_units(mode, b.clip);
     uint64_t* hd_out = nullptr;
     // counters / frame flags / bit exports without APP: the bit-sliced kernel when it applies
     // (its export build stores every iteration's hard decisions, bit-sliced, in ws.hdx)
-    const bool bs = !b.app_out && !b.awgn && use_bs(g, mode, b.T, ucn, per_edge_w != 0, b.clip);
+    const bool bs = !b.app_out && !b.awgn && use_bs(g, r);
     if (b.q8 && !bs) return LDPC_ERR_UNSUPPORTED;          // the in-prologue channel is the bit-sliced kernels'
 
     ws.bits_packed = false;
     if (want_bits) {
-        const size_t elems = (size_t)(T_max + 1) * ntiles_max * g.n_vars * 4;
-        if ((int64_t)elems > ws.hd_elems) {
-            if (ws.hd) (void)hipFree(ws.hd);
-            ws.hd = nullptr;
-            ws.hd_elems = 0;
-            if (hipMalloc(reinterpret_cast<void**>(&ws.hd), elems * sizeof(uint64_t)) != hipSuccess) {
-                (void)hipGetLastError();
-                return LDPC_ERR_OOM;
-            }
-            ws.hd_elems = (int64_t)elems;
-        }
+        const int sh = dev_grow(ws.hd, ws.hd_elems, (size_t)(T_max + 1) * ntiles_max * g.n_vars * 4);
+        if (sh != LDPC_OK) return sh;
         // the v5 export ORs its bits into a zeroed buffer; a bit-sliced decode reads the tile
         // buffer only for the packs its v5 fixup decodes, and the fixup clears those blocks'
         // bits itself (f5_block), so the (T + 1) x tiles x n_vars x 32 B memset is skipped
@@ -120,35 +120,17 @@ int fused_decode(const DevGraph& g, Bufs& b, FusedWorkspace& ws, const float* ll
     if (bs) {
         // bit-sliced kernel; packs whose LLRs are off the quantizer grid go to the v5 kernel
         const int64_t npk = (b.B + 31) / 32;
-        uint32_t* hdx = nullptr;
-        if (want_bits) {
-            const int64_t n = (int64_t)b.T * npk * g.n_vars;
-            if (n > ws.hdx_elems) {
-                if (ws.hdx) (void)hipFree(ws.hdx);
-                ws.hdx = nullptr;
-                ws.hdx_elems = 0;
-                if (hipMalloc(reinterpret_cast<void**>(&ws.hdx), (size_t)n * 4) != hipSuccess) {
-                    (void)hipGetLastError();
-                    return LDPC_ERR_OOM;
-                }
-                ws.hdx_elems = n;
-            }
-            hdx = ws.hdx;
-        }
-        if (npk > ws.bs_bad_n) {
-            if (ws.bs_bad) (void)hipFree(ws.bs_bad);
-            ws.bs_bad = nullptr;
-            ws.bs_bad_n = 0;
-            const int64_t n = std::max<int64_t>(npk, (int64_t)(ntiles_max) * 8);
-            if (hipMalloc(reinterpret_cast<void**>(&ws.bs_bad), (size_t)n * 4) != hipSuccess) {
-                (void)hipGetLastError();
-                return LDPC_ERR_OOM;
-            }
-            ws.bs_bad_n = n;
-        }
-        int st = bs_decode(g, b, ws, llr, mode, ucn, counters, flags, ws.bs_bad, hdx, false, s);
+        int st = want_bits ? dev_grow(ws.hdx, ws.hdx_elems, (size_t)b.T * npk * g.n_vars) : LDPC_OK;
+        if (st == LDPC_OK) st = ensure_bs_bad(ws, npk, ntiles_max);
         if (st != LDPC_OK) return st;
-        ws.last_kernel = fused_kernel_name(g, mode, b.T, b.clip, ucn, per_edge_w != 0);
+        BsOut o{};
+        o.counters = counters;
+        o.flags = flags;
+        o.bad = ws.bs_bad;
+        o.hdx = want_bits ? ws.hdx : nullptr;
+        st = bs_decode(g, b, ws, llr, r, o, s);
+        if (st != LDPC_OK) return st;
+        ws.last_kernel = bs_kernel_name(g, r);
         ws.bits_packed = want_bits;
         if (b.q8) return LDPC_OK;      // generated channel: every pack is on the grid, nothing to fix up
         // test hook: LDPC_BS_FIXUP=0 skips the v5 fixup, so a test can tell that a batch was
@@ -164,64 +146,30 @@ int fused_decode(const DevGraph& g, Bufs& b, FusedWorkspace& ws, const float* ll
                          counters, flags, s);
 }
 
-bool fused_word_supported(const DevGraph& g, int mode, int T, float clip, bool ucn, bool per_edge_w) {
-    return fused_supported(g, mode, T, clip) && g.n_vars <= WORD_MAX_VARS && use_bs(g, mode, T, ucn, per_edge_w, clip);
+bool fused_bs_supported(const DevGraph& g, const BsReq& r) {
+    if (r.es) return bs_supported(g, r);
+    return fused_supported(g, r.mode, r.T, r.clip) && g.n_vars <= WORD_MAX_VARS && use_bs(g, r);
 }
 
-// the word modes' scratch: one word per (pack, variable) of the largest batch, whatever T is
-static int word_scratch(const DevGraph& g, FusedWorkspace& ws, int64_t B_max) {
-    const int64_t n = ((B_max + 31) / 32) * g.n_vars;
-    if (n > ws.hdw_elems) {
-        if (ws.hdw) (void)hipFree(ws.hdw);
-        ws.hdw = nullptr;
-        ws.hdw_elems = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&ws.hdw), (size_t)n * 4) != hipSuccess) {
-            (void)hipGetLastError();
-            return LDPC_ERR_OOM;
-        }
-        ws.hdw_elems = n;
-    }
-    return LDPC_OK;
-}
-
-int fused_decode_word(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode, bool ucn,
-                      int64_t B_max, int64_t* counters, uint8_t* flags, uint32_t* hard_last,
-                      uint8_t* word_flags, hipStream_t s) {
-    if (!fused_word_supported(g, mode, b.T, b.clip, ucn, false)) return LDPC_ERR_UNSUPPORTED;
-    const int64_t npk_max = (B_max + 31) / 32;
-    const int sw = word_scratch(g, ws, B_max);
-    if (sw != LDPC_OK) return sw;
-    if (npk_max > ws.bs_bad_n) {         // (the kernel's per-pack off-grid word, as fused_decode's)
-        if (ws.bs_bad) (void)hipFree(ws.bs_bad);
-        ws.bs_bad = nullptr;
-        ws.bs_bad_n = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&ws.bs_bad), (size_t)npk_max * 4) != hipSuccess) {
-            (void)hipGetLastError();
-            return LDPC_ERR_OOM;
-        }
-        ws.bs_bad_n = npk_max;
-    }
-    // (off-grid packs are marked by word_out, not decoded: no v5 fixup, so none of its tile buffers)
-    const int st = bs_decode(g, b, ws, llr, mode, ucn, counters, flags, ws.bs_bad, ws.hdw, true, s);
+int fused_decode_bs(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, const BsReq& r,
+                    int64_t B_max, int ntiles_max, BsOut o, uint32_t* rows, uint8_t* word_flags, hipStream_t s) {
+    // (word_out's LDS holds the 4 variables on 1024 lanes that bound every bit-sliced plan)
+    if (!fused_bs_supported(g, r) || (rows && (g.n_vars > WORD_MAX_VARS || b.B > B_max))) return LDPC_ERR_UNSUPPORTED;
+    if (b.q8 && !bs_q8_ok(g, r, reinterpret_cast<const AwgnParams*>(b.gen8)->ss > 0)) return LDPC_ERR_UNSUPPORTED;
+    // the word modes' scratch: one word per (pack, variable) of the largest batch, whatever T is
+    int st = rows ? dev_grow(ws.hdw, ws.hdw_elems, (size_t)((B_max + 31) / 32) * g.n_vars) : LDPC_OK;
+    if (st == LDPC_OK) st = ensure_bs_bad(ws, (b.B + 31) / 32, ntiles_max);
     if (st != LDPC_OK) return st;
-    return word_out(g, ws.hdw, ws.bs_bad, b.B, hard_last, word_flags, flags, s);
-}
-
-int fused_decode_es_word(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, int mode, bool ucn,
-                         int64_t B_max, int ntiles_max, int64_t* counters, uint8_t* flags, uint8_t* n_iter,
-                         int64_t* iter_hist, uint32_t* hard_stop, uint8_t* word_flags, hipStream_t s) {
-    // (nothing allocated or launched for a request the early-stop builds do not serve; word_out's
-    // LDS holds the 4 variables on 1024 lanes that bound every bit-sliced plan)
-    if (!bs_es_supported(g, mode, ucn, false, b.clip, b.T) || g.n_vars > WORD_MAX_VARS || b.B > B_max)
-        return LDPC_ERR_UNSUPPORTED;
-    if (b.q8 && !bs_es_q8_ok(g, mode, ucn, b.clip, b.T, reinterpret_cast<const AwgnParams*>(b.gen8)->ss > 0))
-        return LDPC_ERR_UNSUPPORTED;
-    const int sw = word_scratch(g, ws, B_max);
-    if (sw != LDPC_OK) return sw;
-    // (bs_decode_es sizes ws.bs_bad; both kernels write every pack's off-grid mark into it)
-    const int st = bs_decode_es(g, b, ws, llr, mode, ucn, ntiles_max, counters, flags, n_iter, iter_hist, ws.hdw, s);
-    if (st != LDPC_OK) return st;
-    return word_out(g, ws.hdw, ws.bs_bad, b.B, hard_stop, word_flags, flags, s);
+    // (off-grid packs are marked -- by the kernel, in the rows by word_out --, not decoded: no v5
+    // fixup, so none of its tile buffers)
+    o.bad = ws.bs_bad;
+    if (rows) {
+        (r.es ? o.hdw : o.hdx) = ws.hdw;
+        o.word = !r.es;
+    }
+    st = bs_decode(g, b, ws, llr, r, o, s);
+    if (st != LDPC_OK || !rows) return st;
+    return word_out(g, ws.hdw, ws.bs_bad, b.B, rows, word_flags, o.flags, s);
 }
 
 HdView fused_bits_view(const FusedWorkspace& ws) {

@@ -311,15 +311,8 @@ int fused5_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const fl
     const size_t off_grow = off_gad + (size_t)p.ngroups * npk * 64 * 4;
     const size_t tbytes = off_grow + (size_t)p.ngroups * 16;
     if (tbytes > ws.tables_bytes) {
-        if (ws.tables) (void)hipFree(ws.tables);
-        ws.tables = nullptr;
-        ws.tables_bytes = 0;
         ws.key_gad[0] = ws.key_qtab[0] = ~0ull;
-        if (hipMalloc(&ws.tables, tbytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return LDPC_ERR_OOM;
-        }
-        ws.tables_bytes = tbytes;
+        if (dev_grow(ws.tables, ws.tables_bytes, tbytes, 1) != LDPC_OK) return LDPC_ERR_OOM;
     }
     uint16_t* qtab = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(ws.tables) + off_qt);
     uint32_t* gad = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(ws.tables) + off_gad);

@@ -83,6 +83,44 @@ static ldpc_decode_params make_params(int T, int decoding_type, int q_bit, int t
     return p;
 }
 
+static ldpc_channel_params make_channel(double sigma, uint64_t seed, int64_t offset, int ps, int pe,
+                                        int ss, int se) {
+    ldpc_channel_params ch{};
+    ch.sigma = sigma;
+    ch.seed = seed;
+    ch.offset = offset;
+    ch.punct_start = ps;
+    ch.punct_end = pe;
+    ch.short_start = ss;
+    ch.short_end = se;
+    return ch;
+}
+
+static ldpc_es_outputs make_es_outputs(uintptr_t counters, uintptr_t flags, uintptr_t n_iter,
+                                       uintptr_t iter_hist) {
+    ldpc_es_outputs o{};
+    o.size = (int32_t)sizeof(ldpc_es_outputs);
+    o.counters = reinterpret_cast<int64_t*>(counters);
+    o.frame_flags = reinterpret_cast<uint8_t*>(flags);
+    o.n_iter = reinterpret_cast<uint8_t*>(n_iter);
+    o.iter_hist = reinterpret_cast<int64_t*>(iter_hist);
+    return o;
+}
+
+static ldpc_es_word_outputs make_es_word_outputs(uintptr_t hard_stop, uintptr_t word_flags,
+                                                 uintptr_t counters, uintptr_t flags, uintptr_t n_iter,
+                                                 uintptr_t iter_hist) {
+    ldpc_es_word_outputs o{};
+    o.size = (int32_t)sizeof(ldpc_es_word_outputs);
+    o.hard_stop = reinterpret_cast<uint32_t*>(hard_stop);
+    o.word_flags = reinterpret_cast<uint8_t*>(word_flags);
+    o.counters = reinterpret_cast<int64_t*>(counters);
+    o.frame_flags = reinterpret_cast<uint8_t*>(flags);
+    o.n_iter = reinterpret_cast<uint8_t*>(n_iter);
+    o.iter_hist = reinterpret_cast<int64_t*>(iter_hist);
+    return o;
+}
+
 PYBIND11_MODULE(_ldpc_nms, m) {
     m.doc() = "pybind11 binding of the MI355X NMS LDPC decoder C ABI";
     m.def("abi_version", &ldpc_abi_version);
@@ -125,14 +163,7 @@ PYBIND11_MODULE(_ldpc_nms, m) {
            int kernel, double sigma, uint64_t seed, int64_t offset, int ps, int pe, int ss, int se,
            uintptr_t app, uintptr_t counters, uintptr_t flags, uintptr_t stream, uintptr_t iter_wrong) {
             ldpc_decode_params p = make_params(T, decoding_type, q_bit, target_bits, clip, kernel);
-            ldpc_channel_params ch{};
-            ch.sigma = sigma;
-            ch.seed = seed;
-            ch.offset = offset;
-            ch.punct_start = ps;
-            ch.punct_end = pe;
-            ch.short_start = ss;
-            ch.short_end = se;
+            ldpc_channel_params ch = make_channel(sigma, seed, offset, ps, pe, ss, se);
             ldpc_decode_outputs o{};
             o.app_all = reinterpret_cast<float*>(app);
             o.counters = reinterpret_cast<int64_t*>(counters);
@@ -157,12 +188,7 @@ PYBIND11_MODULE(_ldpc_nms, m) {
            float clip, int kernel, uintptr_t counters, uintptr_t flags, uintptr_t n_iter,
            uintptr_t iter_hist, uintptr_t stream) {
             ldpc_decode_params p = make_params(T, decoding_type, q_bit, target_bits, clip, kernel);
-            ldpc_es_outputs o{};
-            o.size = (int32_t)sizeof(ldpc_es_outputs);
-            o.counters = reinterpret_cast<int64_t*>(counters);
-            o.frame_flags = reinterpret_cast<uint8_t*>(flags);
-            o.n_iter = reinterpret_cast<uint8_t*>(n_iter);
-            o.iter_hist = reinterpret_cast<int64_t*>(iter_hist);
+            ldpc_es_outputs o = make_es_outputs(counters, flags, n_iter, iter_hist);
             int st;
             {
                 py::gil_scoped_release nogil;
@@ -181,20 +207,8 @@ PYBIND11_MODULE(_ldpc_nms, m) {
            int kernel, double sigma, uint64_t seed, int64_t offset, int ps, int pe, int ss, int se,
            uintptr_t counters, uintptr_t flags, uintptr_t n_iter, uintptr_t iter_hist, uintptr_t stream) {
             ldpc_decode_params p = make_params(T, decoding_type, q_bit, target_bits, clip, kernel);
-            ldpc_channel_params ch{};
-            ch.sigma = sigma;
-            ch.seed = seed;
-            ch.offset = offset;
-            ch.punct_start = ps;
-            ch.punct_end = pe;
-            ch.short_start = ss;
-            ch.short_end = se;
-            ldpc_es_outputs o{};
-            o.size = (int32_t)sizeof(ldpc_es_outputs);
-            o.counters = reinterpret_cast<int64_t*>(counters);
-            o.frame_flags = reinterpret_cast<uint8_t*>(flags);
-            o.n_iter = reinterpret_cast<uint8_t*>(n_iter);
-            o.iter_hist = reinterpret_cast<int64_t*>(iter_hist);
+            ldpc_channel_params ch = make_channel(sigma, seed, offset, ps, pe, ss, se);
+            ldpc_es_outputs o = make_es_outputs(counters, flags, n_iter, iter_hist);
             int st;
             {
                 py::gil_scoped_release nogil;
@@ -225,14 +239,7 @@ PYBIND11_MODULE(_ldpc_nms, m) {
            float clip, int kernel, uintptr_t hard_stop, uintptr_t word_flags, uintptr_t counters,
            uintptr_t flags, uintptr_t n_iter, uintptr_t iter_hist, uintptr_t stream) {
             ldpc_decode_params p = make_params(T, decoding_type, q_bit, target_bits, clip, kernel);
-            ldpc_es_word_outputs o{};
-            o.size = (int32_t)sizeof(ldpc_es_word_outputs);
-            o.hard_stop = reinterpret_cast<uint32_t*>(hard_stop);
-            o.word_flags = reinterpret_cast<uint8_t*>(word_flags);
-            o.counters = reinterpret_cast<int64_t*>(counters);
-            o.frame_flags = reinterpret_cast<uint8_t*>(flags);
-            o.n_iter = reinterpret_cast<uint8_t*>(n_iter);
-            o.iter_hist = reinterpret_cast<int64_t*>(iter_hist);
+            ldpc_es_word_outputs o = make_es_word_outputs(hard_stop, word_flags, counters, flags, n_iter, iter_hist);
             int st;
             {
                 py::gil_scoped_release nogil;
@@ -252,22 +259,8 @@ PYBIND11_MODULE(_ldpc_nms, m) {
            uintptr_t hard_stop, uintptr_t word_flags, uintptr_t counters, uintptr_t flags,
            uintptr_t n_iter, uintptr_t iter_hist, uintptr_t stream) {
             ldpc_decode_params p = make_params(T, decoding_type, q_bit, target_bits, clip, kernel);
-            ldpc_channel_params ch{};
-            ch.sigma = sigma;
-            ch.seed = seed;
-            ch.offset = offset;
-            ch.punct_start = ps;
-            ch.punct_end = pe;
-            ch.short_start = ss;
-            ch.short_end = se;
-            ldpc_es_word_outputs o{};
-            o.size = (int32_t)sizeof(ldpc_es_word_outputs);
-            o.hard_stop = reinterpret_cast<uint32_t*>(hard_stop);
-            o.word_flags = reinterpret_cast<uint8_t*>(word_flags);
-            o.counters = reinterpret_cast<int64_t*>(counters);
-            o.frame_flags = reinterpret_cast<uint8_t*>(flags);
-            o.n_iter = reinterpret_cast<uint8_t*>(n_iter);
-            o.iter_hist = reinterpret_cast<int64_t*>(iter_hist);
+            ldpc_channel_params ch = make_channel(sigma, seed, offset, ps, pe, ss, se);
+            ldpc_es_word_outputs o = make_es_word_outputs(hard_stop, word_flags, counters, flags, n_iter, iter_hist);
             int st;
             {
                 py::gil_scoped_release nogil;

@@ -182,30 +182,11 @@ class NMSDecoder:
             raise ValueError("on_off_grid must be 'raise' or 'mark'")
         llr = self._as_llr(llr)
         B = int(llr.shape[0])
-        nw = (self.n_vars + 31) // 32
-        res = DecodeResult()
-        if isinstance(hard_last, torch.Tensor):             # caller-owned int32 [>= B, nw]
-            if (hard_last.dtype != torch.int32 or hard_last.device != dev or hard_last.dim() != 2 or
-                    hard_last.shape[0] < B or hard_last.shape[1] != nw or not hard_last.is_contiguous()):
-                raise ValueError(f"hard_last must be a contiguous int32 [>= B, {nw}] tensor on the decoder's device")
-            res.hard_last = hard_last
-        else:
-            res.hard_last = torch.empty((B, nw), dtype=torch.int32, device=dev)
+        res = self._word_result(B, hard_last)
         want_wf = word_flags or on_off_grid == "raise"
         if want_wf:
             res.word_flags = torch.empty(B, dtype=torch.uint8, device=dev)
-        if counters is True:
-            counters = torch.zeros(4, dtype=torch.int64, device=dev)
-        if counters is not None:
-            if counters.dtype != torch.int64 or counters.numel() < 4 or counters.device != dev:
-                raise ValueError("counters must be an int64[4] tensor on the decoder's device")
-            res.counters = counters
-        if isinstance(flags, torch.Tensor):
-            if flags.dtype != torch.uint8 or flags.device != dev or flags.numel() < B:
-                raise ValueError("flags tensor must be uint8 on the decoder's device, >= B long")
-            res.flags = flags
-        elif flags:
-            res.flags = torch.empty(B, dtype=torch.uint8, device=dev)
+        self._es_outputs(res, B, T, counters, flags, False, None)
         if B == 0:
             return res
         ctx = self._ensure_ctx(B, T)
@@ -216,14 +197,36 @@ class NMSDecoder:
                               KERNELS[kernel or self.kernel], res.hard_last.data_ptr(), ptr(res.word_flags),
                               ptr(res.counters), ptr(res.flags), stream.cuda_stream)
         if on_off_grid == "raise":
-            stream.synchronize()
-            nbad = int((res.word_flags == 0x80).sum().item())
-            if nbad:
-                raise ValueError(f"hard_last: {nbad} frames are in packs with LLRs off the quantizer "
-                                 "grid and were not decoded (on_off_grid='mark' returns them marked)")
-            if not word_flags:
-                res.word_flags = None
+            self._raise_off_grid(res, stream, "hard_last", word_flags)
         return res
+
+    def _word_result(self, B, hard_last):
+        """A result with the word modes' rows: ``hard_last`` itself when it is a caller-owned
+        contiguous int32 [>= B, ceil(n_vars / 32)] tensor (checked), else B new rows."""
+        torch = self._torch
+        dev = self.device
+        nw = (self.n_vars + 31) // 32
+        res = DecodeResult()
+        if isinstance(hard_last, torch.Tensor):
+            if (hard_last.dtype != torch.int32 or hard_last.device != dev or hard_last.dim() != 2 or
+                    hard_last.shape[0] < B or hard_last.shape[1] != nw or not hard_last.is_contiguous()):
+                raise ValueError(f"hard_last must be a contiguous int32 [>= B, {nw}] tensor on the decoder's device")
+            res.hard_last = hard_last
+        else:
+            res.hard_last = torch.empty((B, nw), dtype=torch.int32, device=dev)
+        return res
+
+    @staticmethod
+    def _raise_off_grid(res, stream, what, keep_word_flags):
+        """``on_off_grid="raise"`` of the word modes: wait for the decode, raise when
+        ``res.word_flags`` marks frames of a pack off the grid, and drop the flags if unasked."""
+        stream.synchronize()
+        nbad = int((res.word_flags == 0x80).sum().item())
+        if nbad:
+            raise ValueError(f"{what}: {nbad} frames are in packs with LLRs off the quantizer "
+                             "grid and were not decoded (on_off_grid='mark' returns them marked)")
+        if not keep_word_flags:
+            res.word_flags = None
 
     def _decode_es_word(self, llr, B, T, nt, hard_last, word_flags, counters, flags, n_iter, iter_hist,
                         kernel, stream, on_off_grid, channel=None):
@@ -234,15 +237,7 @@ class NMSDecoder:
         dev = self.device
         if on_off_grid not in ("raise", "mark"):
             raise ValueError("on_off_grid must be 'raise' or 'mark'")
-        nw = (self.n_vars + 31) // 32
-        res = DecodeResult()
-        if isinstance(hard_last, torch.Tensor):             # caller-owned int32 [>= B, nw]
-            if (hard_last.dtype != torch.int32 or hard_last.device != dev or hard_last.dim() != 2 or
-                    hard_last.shape[0] < B or hard_last.shape[1] != nw or not hard_last.is_contiguous()):
-                raise ValueError(f"hard_last must be a contiguous int32 [>= B, {nw}] tensor on the decoder's device")
-            res.hard_last = hard_last
-        else:
-            res.hard_last = torch.empty((B, nw), dtype=torch.int32, device=dev)
+        res = self._word_result(B, hard_last)
         # (the generated channel is always on the grid)
         want_wf = word_flags or (on_off_grid == "raise" and channel is None)
         if want_wf:
@@ -265,17 +260,12 @@ class NMSDecoder:
         self._ext.decode_es_word(ctx, llr.data_ptr(), B, T, self.decoding_type, self.q_bit, nt, self.clip,
                                  KERNELS[kernel or self.kernel], *outs)
         if on_off_grid == "raise":
-            stream.synchronize()
-            nbad = int((res.word_flags == 0x80).sum().item())
-            if nbad:
-                raise ValueError(f"early_stop: {nbad} frames are in packs with LLRs off the quantizer "
-                                 "grid and were not decoded (on_off_grid='mark' returns them marked)")
-            if not word_flags:
-                res.word_flags = None
+            self._raise_off_grid(res, stream, "early_stop", word_flags)
         return res
 
     def _es_outputs(self, res, B, T, counters, flags, n_iter, iter_hist):
-        """The early-stop decode's output tensors into ``res`` (caller-owned ones checked)."""
+        """The output tensors of an early-stop or word decode into ``res`` (caller-owned ones
+        checked; the word mode has no ``n_iter`` / ``iter_hist``)."""
         torch = self._torch
         dev = self.device
         if counters is True:
