@@ -127,6 +127,12 @@ int ldpc_kernel_info(const ldpc_ctx* c, const ldpc_decode_params* p, int64_t* by
    separate build of the same kernel that also stores each iteration's hard decisions. */
 int ldpc_ctx_last_kernel(const ldpc_ctx* c, char* name, int32_t name_len);
 
+/* 1 when the last successful decode on this context ran a geometry-frozen build of its bit-sliced
+   kernel (the graph's pack geometry as compile-time constants; same name, same results), 0 when it
+   ran the generic build or another kernel; LDPC_ERR_ARG for a null context.  The environment
+   variable LDPC_BS_FROZEN=0, read at every launch, forces the generic build. */
+int ldpc_ctx_last_frozen(const ldpc_ctx* c);
+
 /* On-GPU AWGN channel for the all-zero codeword (create_mix_epoch, Print_Functions.py:29-72):
    writes llr_dev [B][n_vars] f32 = Q(2(sigma*n - 1)/sigma^2) with punctured (1-based bits
    punct_start..punct_end, 0 = none) -> 0 and shortened -> -clip_llr.  Counter-based Philox

@@ -36,6 +36,17 @@ int ldpc_debug_bs_bounds(const int32_t* proto, int32_t M, int32_t N, int32_t z, 
                          int32_t mode, int32_t alpha_uniform, int32_t beta_uniform, float clip,
                          int32_t flags, int32_t* violations, char* msg, int32_t msg_len);
 
+/* The dispatch of the geometry-frozen builds of the bit-sliced kernel (csrc/ldpc_bs_frozen.h) for a
+ * request on a proto graph: kind 0 a plain decode, 1 early stop, 2 the export / word builds; ucn:
+ * UCN weights set.  plan / frozen [n]: the frozen fields as the request's plan has them (-1 without
+ * a bsl plan) and as the frozen builds fix them; names: the fields' names, comma-separated.
+ * Returns 1 when a frozen build serves the request, 0 when not, or a negative status.  Honours
+ * LDPC_BS_FROZEN=0 as a launch does. */
+int ldpc_debug_bs_frozen(const int32_t* proto, int32_t M, int32_t N, int32_t z, int32_t T, int32_t mode,
+                         int32_t alpha_uniform, int32_t beta_uniform, int32_t ucn, int32_t kind,
+                         float clip, int32_t* plan, int32_t* frozen, int32_t n, char* names,
+                         int32_t names_len);
+
 #ifdef __cplusplus
 }
 #endif

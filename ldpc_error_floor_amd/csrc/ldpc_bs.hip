@@ -267,6 +267,49 @@ BsPlan bs_plan(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float cli
     return p;
 }
 
+// ---- the geometry-frozen builds (ldpc_bs_frozen.h) --------------------------------
+// The fields a frozen build fixes, of a plan and of BsFrozenWman, in one order (bs_frozen_names).
+typedef std::array<int32_t, kBsFrozenFields> BsGeoFields;
+static const char* const bs_frozen_names[kBsFrozenFields] = {
+    "inst", "n_vars", "n_checks", "z", "N", "cn_lanes", "cn_dmin", "NT", "nw", "arows", "bcols", "AL", "BL",
+    "cstride", "off_slots", "off_pad", "off_zero", "off_red", "off_alut", "off_blut", "off_ch", "lds"};
+static BsGeoFields bs_plan_fields(const DevGraph& g, const BsPlan& p) {
+    const int ar = (p.inst >= 0 && kBsInst[p.inst].UCN ? 2 : 1) * p.arows;
+    return {p.inst, g.n_vars, g.n_checks, g.z, g.N, p.cn_lanes, p.cn_dmin, 64 * p.nw, p.nw, p.arows, p.bcols,
+            ar * LUT_W, p.bcols * BLUT_W, g.z * SLOT_B, (int32_t)p.off_slots, (int32_t)p.off_pad,
+            (int32_t)p.off_zero, (int32_t)p.off_red, (int32_t)p.off_alut, (int32_t)p.off_blut,
+            (int32_t)p.off_ch, (int32_t)p.lds};
+}
+static BsGeoFields bs_frozen_fields() {
+    typedef BsFrozenWman W;
+    return {W::inst, W::n_vars, W::n_checks, W::z, W::N, W::cn_lanes, W::cn_dmin, W::NT, W::nw, W::arows,
+            W::bcols, W::AL, W::BL, (int32_t)W::cstride, (int32_t)W::off_slots, (int32_t)W::off_pad,
+            (int32_t)W::off_zero, (int32_t)W::off_red, (int32_t)W::off_alut, (int32_t)W::off_blut,
+            (int32_t)W::off_ch, (int32_t)W::lds};
+}
+// The frozen builds serve a plain decode (counters / flags / iter_wrong, from LLRs or the
+// in-prologue channel) whose plan equals BsFrozenWman field by field; every other request -- another
+// graph or lifting, UCN or per-row weights, early stop, the export and word builds, more than
+// T_CAP iterations -- runs the generic build of its plan exactly as before.  The plan is bs_plan's,
+// with one change where it fits: RED is sized for T_CAP iterations' frame-error words whatever T
+// <= T_CAP is (plan_inst sizes it for T, rounded to 16 B, and puts the tables and the per-lane
+// words after it), so one set of literals serves every such T.  LDPC_BS_FROZEN=0 forces the generic
+// build (A/B and tests; read at every launch).
+static bool bs_frozen_fit(const DevGraph& g, BsPlan& p, const BsReq& r, bool exports) {
+    const char* e = getenv("LDPC_BS_FROZEN");
+    if (e && atoi(e) == 0) return false;
+    if (!p.ok || p.inst != BsFrozenWman::inst || p.ucn || r.es || exports || r.T > BsFrozenWman::T_CAP) return false;
+    BsPlan q = p;
+    const uint32_t d = (uint32_t)(((4 * BsFrozenWman::T_CAP + 15) & ~15) - ((4 * r.T + 15) & ~15));
+    q.off_alut += d;
+    q.off_blut += d;
+    q.off_ch += d;
+    q.lds += d;
+    if (bs_plan_fields(g, q) != bs_frozen_fields()) return false;
+    p = q;
+    return true;
+}
+
 // Deal `n` chunks (costs `cost`) to nw waves with at most `cap` chunks per wave (slot[w][c] =
 // chunk or -1; wave w runs on SIMD w mod 4).  The chunks of one phase end at a barrier, and a
 // SIMD's last busy wave runs alone, latency-bound (a dependent chain issues every ~8.5 cycles
@@ -765,8 +808,10 @@ const char* bs_kernel_name(const DevGraph& g, const BsReq& r) {
 }
 
 // one launch of plan p (an ES instance's plan for an early-stop request)
+// (frozen: p passed bs_frozen_fit, the geometry-frozen build decodes it)
 static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const BsPlan& p, const float* llr,
-                  const BsReq& r, const BsOut& o, hipStream_t s) {
+                  const BsReq& r, const BsOut& o, bool frozen, hipStream_t s) {
+    ws.bs_frozen = frozen;
     // (the early-stop instances' graph tables: a pair of their own)
     void*& graph = r.es ? ws.bs_es_graph : ws.bs_graph;
     int st = bs_graph_tables(g, p, graph, r.es ? ws.bs_es_graph_inst : ws.bs_graph_inst, s);
@@ -785,6 +830,7 @@ static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const Bs
     a.iter_hist = o.iter_hist;
     a.hdw = o.hdw;
     a.word = o.word ? 1 : 0;
+    a.frozen = frozen;
     a.llr = llr;
     a.gen = bs_gen(b, q8_tab_lds(p));    // the in-prologue channel (ldpc_decode_awgn)
     a.B = b.B;
@@ -848,7 +894,7 @@ static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const Bs
     const uint64_t rkey = (uint64_t)p.inst << 48 | (uint64_t)p.nw << 32 | (uint64_t)lds;
     if (ws.bs_resident_key != rkey) {
         ws.bs_resident_key = rkey;
-        std::fill(ws.bs_resident, ws.bs_resident + 3, 0);
+        std::fill(ws.bs_resident, ws.bs_resident + 5, 0);
     }
 #ifdef BS_STAMP
     // diagnostic build: per-wave phase clocks of this decode, printed to stderr
@@ -861,8 +907,9 @@ static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const Bs
     if (st != LDPC_OK || hipMemcpyAsync(hst, dst, sizeof(hst), hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
         return st != LDPC_OK ? st : LDPC_ERR_HIP;
-    fprintf(stderr, "bs_stamp inst %d T %d q8 %d: per pack, shader clocks [check, check-barrier, var, var-barrier | "
-            "entry, channel, ch-barrier, tables, first-var, check-setup | epilogue]\n", p.inst, b.T, b.q8 != nullptr);
+    fprintf(stderr, "bs_stamp inst %d T %d q8 %d frozen %d: per pack, shader clocks [check, check-barrier, var, var-barrier | "
+            "entry, channel, ch-barrier, tables, first-var, check-setup | epilogue]\n", p.inst, b.T, b.q8 != nullptr,
+            (int)frozen);
     static const int order[] = {0, 1, 2, 3, 8, 9, 10, 11, 12, 4, 5};
     for (int w = 0; w < p.nw && w < 16; ++w) {
         const double n = (double)(hst[16 * w + 15] ? hst[16 * w + 15] : 1);
@@ -880,9 +927,11 @@ static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const Bs
 int bs_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, const BsReq& r,
               const BsOut& o, hipStream_t s) {
     bool to_bsc;
-    const BsPlan p = bs_route(g, r, &to_bsc);
+    BsPlan p = bs_route(g, r, &to_bsc);
+    ws.bs_frozen = false;
     if (!p.ok) return to_bsc ? bsc_decode(g, b, ws, llr, r, o, s) : LDPC_ERR_UNSUPPORTED;
-    return bs_run(g, b, ws, p, llr, r, o, s);
+    const bool frozen = bs_frozen_fit(g, p, r, o.hdx != nullptr || o.hdw != nullptr);
+    return bs_run(g, b, ws, p, llr, r, o, frozen, s);
 }
 
 }  // namespace ldpc
@@ -1064,6 +1113,48 @@ static int bs_bounds_check(const DevGraph& g, const BsPlan& p, const BsHostTable
 }
 }  // namespace bs
 }  // namespace ldpc
+
+// The geometry-frozen builds' dispatch (bs_frozen_fit) for a request on a proto graph, host only.
+// kind: 0 a plain decode, 1 early stop, 2 the export / word builds.  plan / frozen [n]: the fields
+// of the request's plan (RED sized as the frozen builds take it where the rest fits) and of
+// BsFrozenWman, names: their names, comma-separated.  Returns 1 when a frozen build serves the
+// request, 0 when the generic one does or no bsl plan at all, a negative status on bad arguments.
+extern "C" int ldpc_debug_bs_frozen(const int32_t* proto, int32_t M, int32_t N, int32_t z, int32_t T,
+                                    int32_t mode, int32_t alpha_uniform, int32_t beta_uniform, int32_t ucn,
+                                    int32_t kind, float clip, int32_t* plan, int32_t* frozen, int32_t n,
+                                    char* names, int32_t names_len) {
+    using namespace ldpc;
+    using namespace ldpc::bs;
+    if (!proto || T <= 0 || kind < 0 || kind > 2 || n < 0) return LDPC_ERR_ARG;
+    host::GraphTables h;
+    const int st = host::build_graph(proto, M, N, z, h);
+    if (st != LDPC_OK) return st;
+    DevGraph g{};
+    g.M = h.M; g.N = h.N; g.z = h.z; g.E = h.E;
+    g.n_checks = h.M * h.z; g.n_vars = h.N * h.z; g.n_edges = h.E * h.z; g.max_cdeg = h.max_cdeg;
+    g.h_row_ptr = h.row_ptr.data();
+    g.host = &h;
+    g.w_alpha_uniform = alpha_uniform;
+    g.w_alpha_pair_uniform = alpha_uniform;
+    g.w_beta_uniform = beta_uniform;
+    g.w_beta_nonneg = 1;
+    const BsReq r{mode, ucn != 0, false, clip, T, kind == 1};
+    bool to_bsc;
+    BsPlan p = bs_route(g, r, &to_bsc);
+    const bool fz = bs_frozen_fit(g, p, r, kind == 2);
+    const BsGeoFields pf = bs_plan_fields(g, p), ff = bs_frozen_fields();
+    for (int i = 0; i < n && i < kBsFrozenFields; ++i) {
+        if (plan) plan[i] = p.ok ? pf[(size_t)i] : -1;
+        if (frozen) frozen[i] = ff[(size_t)i];
+    }
+    if (names && names_len > 0) {
+        std::string all;
+        for (int i = 0; i < kBsFrozenFields; ++i) all += std::string(i ? "," : "") + bs_frozen_names[i];
+        std::strncpy(names, all.c_str(), (size_t)names_len - 1);
+        names[names_len - 1] = 0;
+    }
+    return fz ? 1 : 0;
+}
 
 // One plan per (instance, UCN) that fits a proto graph with the given weight properties, each
 // checked by bs_bounds_check.  Returns the number of plans checked (>= 0) and writes the first

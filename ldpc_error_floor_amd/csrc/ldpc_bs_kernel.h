@@ -37,6 +37,7 @@
 #include "ldpc_fused.h"
 #include "ldpc_fused5_kernel.h"
 #include "ldpc_bitplane.h"
+#include "ldpc_bs_frozen.h"
 
 namespace ldpc {
 namespace bs {
@@ -613,12 +614,12 @@ constexpr bool bs_loops(const BsInst& k) { return k.VPL == 1 && k.CPL == 1 && !k
     const int64_t b0 = (int64_t)(pk) * PACK;                                                       \
     const int nvalid = (int)min<int64_t>(PACK, a.B - b0);                                          \
     const uint32_t valid = (nvalid >= 32) ? 0xFFFFFFFFu : ((1u << nvalid) - 1u);                   \
-    uint32_t* RED = reinterpret_cast<uint32_t*>(smem + a.off_red);                                 \
+    uint32_t* RED = reinterpret_cast<uint32_t*>(smem + (FZ ? W::off_red : a.off_red));             \
     const int flor = 16 + ((a.T + 3) & ~3);                                                        \
-    const int AR = UCN ? 2 * a.arows : a.arows;                                                    \
-    const int AL = AR * LUT_W, BL = a.bcols * BLUT_W;                                              \
-    uint32_t* ALUT = reinterpret_cast<uint32_t*>(smem + a.off_alut);                               \
-    uint32_t* BLUT = reinterpret_cast<uint32_t*>(smem + a.off_blut);                               \
+    const int AR = UCN ? 2 * (FZ ? W::arows : a.arows) : (FZ ? W::arows : a.arows);                \
+    const int AL = AR * LUT_W, BL = (FZ ? W::bcols : a.bcols) * BLUT_W;                            \
+    uint32_t* ALUT = reinterpret_cast<uint32_t*>(smem + (FZ ? W::off_alut : a.off_alut));          \
+    uint32_t* BLUT = reinterpret_cast<uint32_t*>(smem + (FZ ? W::off_blut : a.off_blut));          \
     const bool ucn = UCN && a.ucn;                                                                 \
     auto ucn_on = [&](int t) __attribute__((always_inline)) -> bool {                              \
         return ucn && (t >= 64 || ((a.ucn_iter >> t) & 1));                                        \
@@ -640,13 +641,22 @@ constexpr bool bs_loops(const BsInst& k) { return k.VPL == 1 && k.CPL == 1 && !k
 // iteration; a pack leaves the T loop once each of its codewords has had a zero syndrome, and the
 // epilogue takes every codeword's outputs at its own first zero-syndrome iteration.
 template <int D, int DV, int LPC, int VPL, int CPL, bool UCN, bool BIG, bool PK, int WPE, bool XP, int LB, bool Q8,
-          bool ES = false, bool EW = false>
+          bool ES = false, bool EW = false, bool FZ = false>
 __global__ void __launch_bounds__(LB) __attribute__((amdgpu_waves_per_eu(WPE)))
 k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::conditional_t<XP, BsArgsXp, BsArgs>> a) {
     static_assert(LPC == 2 || LPC == 4, "lanes per check");
     using KArgs = std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::conditional_t<XP, BsArgsXp, BsArgs>>;
     static_assert(!ES || (UCN && VPL == 1 && CPL == 1 && !XP), "early stop: one-chunk UCN-compiled instances");
     static_assert(!EW || ES, "the stop-iteration word: early-stop builds");
+    // FZ: the geometry-frozen build (ldpc_bs_frozen.h): the pack geometry is W's literals instead
+    // of kernel arguments, (FZ ? W::x : a.x) at each read -- written out, not behind an accessor:
+    // through one the other builds' code changed; the pack-loop decode and in-prologue channel
+    // builds of wman
+    static_assert(!FZ || (BS_LOOP_TU && !UCN && !XP && !ES && VPL == 1 && CPL == 1 && D == 15 && DV == 6 && LPC == 4),
+                  "frozen geometry: the wman pack-loop builds");
+    using W = BsFrozenWman;
+    static_assert(W::cstride == W::z * SLOT_B && W::AL == W::arows * LUT_W && W::BL == W::bcols * BLUT_W &&
+                  W::NT == 64 * W::nw && W::off_zero == W::off_pad + SLOT_B, "BsFrozenWman is consistent");
     constexpr int SB = (DV * QMAX + QMAX <= 127) ? 8 : 9;     // planes of S and of lw + S
     constexpr int EPL = (D + LPC - 1) / LPC;                     // edge slots per check lane
     constexpr bool SKIPM = CPL > 1;                              // chunk-wide padding skipped
@@ -696,11 +706,11 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
 #define BS_ST(i) ((void)0)
 #endif
     const int tid = threadIdx.x;
-    const int NT = blockDim.x;
+    const int NT = FZ ? W::NT : (int)blockDim.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nwv = NT >> 6;
-    const int nv = a.n_vars;
+    const int nv = (FZ ? W::n_vars : a.n_vars);
 #if !BS_LOOP_TU
     BS_PACK_SETUP(blockIdx.x)
 #endif
@@ -719,7 +729,7 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
         dw[u] = __builtin_amdgcn_readfirstlane(a.vn_wdeg[3 * (u * nwv + wave)]);
         dwmin[u] = __builtin_amdgcn_readfirstlane(a.vn_wdeg[3 * (u * nwv + wave) + 1]);
         pcol[u] = __builtin_amdgcn_readfirstlane(a.vn_wdeg[3 * (u * nwv + wave) + 2]);
-        tab_b[u] = (a.bcols > 1 && vv[u] >= 0) ? (uint32_t)(((UCN ? (vv[u] & 0xFFFF) : vv[u]) / (nv / a.bcols)) * BLUT_W * 4) : 0u;
+        tab_b[u] = ((FZ ? W::bcols : a.bcols) > 1 && vv[u] >= 0) ? (uint32_t)(((UCN ? (vv[u] & 0xFFFF) : vv[u]) / (nv / (FZ ? W::bcols : a.bcols))) * BLUT_W * 4) : 0u;
     }
     // (the pack loop's units: bit 8 marks the wave that folds the frame-error words in the T loop,
     // a.fold_wave, carried in a word the loop holds anyway -- there the arguments are read through
@@ -727,7 +737,7 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
     // every wave, every iteration; degrees are below 256.  The other units compare a.fold_wave,
     // which they hold in SGPRs: carrying the mark cost the 802.11n early-stop build 7 reloads.)
     constexpr int FOLDB = BS_LOOP_TU ? 0x100 : 0;
-    int cn_dmin = a.cn_dmin | ((FOLDB && (uint32_t)wave == a.fold_wave) ? FOLDB : 0);
+    int cn_dmin = (FZ ? W::cn_dmin : a.cn_dmin) | ((FOLDB && (uint32_t)wave == a.fold_wave) ? FOLDB : 0);
 
     // ---- channel planes: the lane's variables for the 32 codewords of the pack ------------------
     // (no __syncthreads_or: it allocates static LDS, which would move the dynamic LDS base
@@ -773,10 +783,15 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
     PackArgs& a = *kap;
     const int tid = wave * 64 + lane_now(), lane = tid & 63;
     BS_PACK_SETUP(pack)
+    // (the frozen builds read the counted bits once per pack, not at every variable phase: with the
+    // geometry out of the registers there is room to hold it)
+    [[maybe_unused]] const int pack_tbits = FZ ? a.target_bits : 0;
+#define BS_TBITS (FZ ? pack_tbits : a.target_bits)
 #define BS_PK pack
 #define BS_NEXT_PACK continue
 #define BS_LANE_IS0 (lane_now() == 0)
 #else
+#define BS_TBITS a.target_bits
 #define BS_PK blockIdx.x
 #define BS_NEXT_PACK return
 #define BS_LANE_IS0 (lane == 0)
@@ -787,8 +802,8 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
     // loads, retired by the channel barrier (through registers, each thread's loads waited in
     // turn: three L2 round trips and a barrier of their own per pack)
     if (tid < SLOT_W) {
-        reinterpret_cast<uint32_t*>(smem + a.off_pad)[tid] = 0xFFFFFFFFu;
-        reinterpret_cast<uint32_t*>(smem + a.off_zero)[tid] = 0u;
+        reinterpret_cast<uint32_t*>(smem + (FZ ? W::off_pad : a.off_pad))[tid] = 0xFFFFFFFFu;
+        reinterpret_cast<uint32_t*>(smem + (FZ ? W::off_zero : a.off_zero))[tid] = 0u;
     }
     if (UCN && tid == 0) lds_put(a.off_hdz, 0u);
     if (tid < 8) RED[tid] = (tid == 1) ? 0xFFFFFFFFu : 0u;
@@ -841,8 +856,8 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
     uint32_t cs[VPL], cm[VPL][4], bg[VPL];
     int off = 0;
     if (T0A) {                           // (retired by the channel barrier's vmcnt(0))
-        copy_async(a.off_alut, a.alut, AL, wave, NT);
-        copy_async(a.off_blut, a.blut, BL, wave, NT);
+        copy_async((FZ ? W::off_alut : a.off_alut), a.alut, AL, wave, NT);
+        copy_async((FZ ? W::off_blut : a.off_blut), a.blut, BL, wave, NT);
     }
     // all 32 loads of a variable issued before any use: one HBM round trip per workgroup
     // prologue (with batches of 8 the LLR fetch cost 0.75 ms of a 6.5 ms C2 decode, with this
@@ -957,10 +972,10 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
         int bk = -1;
         if constexpr (!XP) {
             if (use_bk && a.btid) {
-                const int col = (a.bcols == 1) ? 0 : pcol[u];
+                const int col = ((FZ ? W::bcols : a.bcols) == 1) ? 0 : pcol[u];
                 if (BKPF) bk = __builtin_amdgcn_readfirstlane(bkp[u]);
                 else if (col >= 0)   // (a scalar load, through the constant address space)
-                    bk = __builtin_amdgcn_readfirstlane((int)((const ConstW*)a.btid)[(size_t)tb * a.btid_n + col]);
+                    bk = __builtin_amdgcn_readfirstlane((int)((const ConstW*)a.btid)[(size_t)tb * (FZ ? W::btid_n : a.btid_n) + col]);
             }
         }
         // identity table: |Q(beta ch)| = |ch| (the mask covers iterations 0..63)
@@ -972,7 +987,7 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
             PH("vn_beta_fix", u);
             beta_asm(lw, cmu, bk);
             if constexpr (BIG) {            // shortened bits: |Q(beta cu)| from the table words
-                if (a.bcols == 1) {
+                if ((FZ ? W::bcols : a.bcols) == 1) {
                     const ConstW* tg = (const ConstW*)(a.blut) + (size_t)tb * BLUT_W;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) lw[i] = mux(bg[u], tg[LUT_W + i], lw[i]);
@@ -984,7 +999,7 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
                     lw[3] = mux(bg[u], gb.w, lw[3]);
                 }
             }
-        } else if (a.bcols == 1) {          // one beta per iteration: table in SGPRs
+        } else if ((FZ ? W::bcols : a.bcols) == 1) {      // one beta per iteration: table in SGPRs
             PH("vn_beta_sg", u);
             const ConstW* tg = (const ConstW*)(a.blut) + (size_t)tb * BLUT_W;
             lut_s(lw, cmu, tg);
@@ -1033,7 +1048,7 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
             const int v = (UCN && vv[u] >= 0) ? (vv[u] & 0xFFFF) : vv[u];
             const uint32_t hda = UCN ? 4u * ((uint32_t)vv[u] >> 16) : 0u;     // HD slot (rotated)
             const uint32_t cmu[4] = {cm[u][0], cm[u][1], cm[u][2], cm[u][3]};
-            const bool counted = v >= 0 && v < a.target_bits;
+            const bool counted = v >= 0 && v < BS_TBITS;
             uint32_t lw[1][4];                   // |Q(beta_{t+1} ch)| (before the C->V: fewer live registers)
             PH("vn_beta", (last ? 100 : 0) + u);
             if (!last) beta_lw(u, bslice, tb, cmu, lw[0], !first);
@@ -1133,7 +1148,7 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
                     abs_sat(X, x);
 #pragma unroll
                     for (int f = 0; f < DV; ++f)
-                        if (f < dwu && (f < dwm || vaddr(f) != a.off_zero)) write_slot(vaddr(f), x[6], X);
+                        if (f < dwu && (f < dwm || vaddr(f) != (FZ ? W::off_zero : a.off_zero))) write_slot(vaddr(f), x[6], X);
                 } else {
 #pragma unroll
                     for (int f = 0; f < DV; ++f) {
@@ -1153,7 +1168,7 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
                             }
                             sub_tv(x, Tv, b, n);
                             abs_sat(X, x);
-                            if (f < dwm || vaddr(f) != a.off_zero) write_slot(vaddr(f), x[6], X);
+                            if (f < dwm || vaddr(f) != (FZ ? W::off_zero : a.off_zero)) write_slot(vaddr(f), x[6], X);
                         }
                     }
                 }
@@ -1192,7 +1207,7 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
         }
     };
 
-    vn_phase(true, false, a.off_blut, 0);
+    vn_phase(true, false, (FZ ? W::off_blut : a.off_blut), 0);
     BS_ST(12);
     // check groups: chunk k of 64 check lanes; lane LPC c + j of it (check c = row i, index h)
     // takes edges k = LPC m + j, at slots first_i + j A_i + m z + h (a.row_lay); edges past the
@@ -1207,16 +1222,16 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
         gchunk[c] = (CPL == 1) ? wave : __builtin_amdgcn_readfirstlane(a.cn_chunk[wave * CPL + c]);
         const int ql = max(gchunk[c], 0) * 64 + lane;
         const int cc = ql / LPC;
-        const int ci = min(cc / a.z, a.n_checks / a.z - 1);
-        gdeg[c] = (cc < a.n_checks) ? a.row_ptr[ci + 1] - a.row_ptr[ci] : 0;
+        const int ci = min(cc / (FZ ? W::z : a.z), (FZ ? W::n_checks : a.n_checks) / (FZ ? W::z : a.z) - 1);
+        gdeg[c] = (cc < (FZ ? W::n_checks : a.n_checks)) ? a.row_ptr[ci + 1] - a.row_ptr[ci] : 0;
         // edge positions m holding a real edge for some lane of the chunk (wave-uniform): the
         // positions past them are padding for every lane and skipped (LPC, an even count, lanes
         // of each group skip together, so the group's [V->C >= 0] parity is unchanged)
         // (the instances with several check chunks per lane: 5G-type graphs, whose rows differ
         // in degree; the one-chunk instances serve near-regular rows and keep their registers)
         gm[c] = SKIPM ? (int)__popc(wave_or((1u << ((gdeg[c] + LPC - 1) / LPC)) - 1u)) : EPL;
-        gbase[c] = a.off_slots + (uint32_t)((a.row_lay[2 * ci] + cj * a.row_lay[2 * ci + 1] + (cc - ci * a.z)) * SLOT_B);
-        gtab[c] = a.off_alut + (uint32_t)((a.arows > 1 ? ci : 0) * LUT_W * 4) + (uint32_t)(cj * OB * 64);
+        gbase[c] = (FZ ? W::off_slots : a.off_slots) + (uint32_t)((a.row_lay[2 * ci] + cj * a.row_lay[2 * ci + 1] + (cc - ci * (FZ ? W::z : a.z))) * SLOT_B);
+        gtab[c] = (FZ ? W::off_alut : a.off_alut) + (uint32_t)(((FZ ? W::arows : a.arows) > 1 ? ci : 0) * LUT_W * 4) + (uint32_t)(cj * OB * 64);
         // (16-bit LDS addresses: the slot base and the alpha-table address share one register
         // through the T loop, unpacked per iteration)
         if constexpr (PKG) gbase[c] |= gtab[c] << 16;
@@ -1224,7 +1239,7 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
 #pragma unroll
             // (the table holds the cn_lanes check lanes: a one-chunk instance's waves past them
             // read nothing -- their reads ran off the end of the allocation)
-            for (int p = 0; p < HDW; ++p) ghd[c][p] = ((ES || ucn) && gchunk[c] >= 0 && ql < a.cn_lanes) ? a.cn_hd[(size_t)ql * HDW + p] : 0u;
+            for (int p = 0; p < HDW; ++p) ghd[c][p] = ((ES || ucn) && gchunk[c] >= 0 && ql < (FZ ? W::cn_lanes : a.cn_lanes)) ? a.cn_hd[(size_t)ql * HDW + p] : 0u;
         }
     }
     // the lane's real edge positions, one word for all its chunks (bit RB c + m: position m of
@@ -1242,12 +1257,12 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
 #pragma unroll
         for (int m = 0; m < EPL; ++m)
             if (RPW && (LPC * m + LPC - 1 < cn_dmin || LPC * m + cj < gdeg[c])) rpk |= 1u << (RB * c + m);
-    const uint32_t cstride = (uint32_t)(a.z * SLOT_B);
-    const uint32_t tabu = (uint32_t)(a.arows * LUT_W * 4);        // alpha' tables after the alpha ones
+    const uint32_t cstride = (uint32_t)((FZ ? W::z : a.z) * SLOT_B);
+    const uint32_t tabu = (uint32_t)((FZ ? W::arows : a.arows) * LUT_W * 4);        // alpha' tables after the alpha ones
     // the one-chunk instances' check-lane slot base (packed with the alpha-table address) kept in
     // one LDS word per lane and read at each check phase, not in a register held through the T loop
     constexpr bool GBL = CPL == 1;
-    if constexpr (GBL) lds_put(a.off_ch + 4u * (uint32_t)tid, gbase[0]);
+    if constexpr (GBL) lds_put((FZ ? W::off_ch : a.off_ch) + 4u * (uint32_t)tid, gbase[0]);
     // the one-chunk UCN instances' packed hard-decision addresses (HDW words per check lane)
     // likewise in LDS, read at each check phase
     constexpr bool HDL = UCN && CPL == 1;
@@ -1277,7 +1292,7 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
 #pragma unroll
         for (int u = 0; u < VPL; ++u) asm volatile("" : "+s"(dw[u]), "+s"(dwmin[u]));   // compared per use, not hoisted as masks
         if (!RPW) asm volatile("" : "+s"(cn_dmin));
-        const int cdm = FOLDB ? (cn_dmin & (FOLDB - 1)) : cn_dmin;    // (without the fold mark)
+        const int cdm = FZ ? W::cn_dmin : FOLDB ? (cn_dmin & (FOLDB - 1)) : cn_dmin;    // (without the fold mark)
         // (the lane's variable made opaque per iteration on the multi-chunk instances: [v >= 0]
         // and [v < target bits] are compared per use, not held through the loop as spilled
         // 64-bit lane masks)
@@ -1292,23 +1307,27 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
             // the copies' wave-uniform bounds made opaque per iteration, so their compares are
             // redone here instead of held through the loop as 64-bit lane masks (not in wman's
             // in-prologue channel build, which ran slower with it)
-            int cw = wave, al = AL, bl = BL, bcl = a.bcols;
-            if (!(Q8 && VPL == 1 && CPL == 1 && !UCN))
+            int cw = wave, al = AL, bl = BL, bcl = (FZ ? W::bcols : a.bcols);
+            // (the frozen builds: the bounds are literals.  The copy loop itself stays: a one-trip
+            // form of it, or the wave count given to the compiler, each brought a VGPR spill back)
+            if (!FZ && !(Q8 && VPL == 1 && CPL == 1 && !UCN))
                 asm volatile("" : "+s"(cw), "+s"(al), "+s"(bl), "+s"(bcl));
             // the tables' addresses loaded again from the kernel arguments each iteration (scalar
             // loads) instead of held through the loop, where they were spilled to VGPR lanes: the
             // one-chunk instances but wman's in-prologue channel build
             const uint32_t* alut_p = a.alut;
             const uint32_t* blut_p = a.blut;
-            uint32_t off_al = a.off_alut, off_bl = a.off_blut;
+            uint32_t off_al = (FZ ? W::off_alut : a.off_alut), off_bl = (FZ ? W::off_blut : a.off_blut);
             if constexpr (VPL == 1 && CPL == 1 && !(Q8 && !UCN)) {
                 typedef __attribute__((address_space(4))) const BsArgs ConstArgs;
                 ConstArgs* ka = (ConstArgs*)__builtin_amdgcn_kernarg_segment_ptr();
                 asm volatile("" : "+s"(ka));
                 alut_p = ka->alut;
                 blut_p = ka->blut;
-                off_al = ka->off_alut;
-                off_bl = ka->off_blut;
+                if constexpr (!FZ) {
+                    off_al = ka->off_alut;
+                    off_bl = ka->off_blut;
+                }
             }
             copy_async(off_al + 4u * (uint32_t)(nx * al), alut_p + (size_t)(t + 1) * al, al, cw, NT);
             if (bcl > 1)
@@ -1318,8 +1337,8 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
             if (t + 1 < a.T && a.btid) {     // (the last variable phase takes no table)
 #pragma unroll
                 for (int u = 0; u < VPL; ++u) {
-                    const int col = (a.bcols == 1) ? 0 : pcol[u];
-                    bkp[u] = col >= 0 ? a.btid[(size_t)(t + 1) * a.btid_n + col] : -1;
+                    const int col = ((FZ ? W::bcols : a.bcols) == 1) ? 0 : pcol[u];
+                    bkp[u] = col >= 0 ? a.btid[(size_t)(t + 1) * (FZ ? W::btid_n : a.btid_n) + col] : -1;
                 }
             }
         }
@@ -1328,7 +1347,7 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
         if (PRIO == 4) __builtin_amdgcn_s_setprio(2);
 #pragma unroll
         for (int c = 0; c < CPL; ++c) {
-            const bool active = (CPL == 1) ? wave * 64 < a.cn_lanes : (gchunk[c] >= 0);   // (cn_lanes: 64 k)
+            const bool active = (CPL == 1) ? (FZ && W::cn_lanes >= W::NT) || wave * 64 < (FZ ? W::cn_lanes : a.cn_lanes) : (gchunk[c] >= 0);   // (cn_lanes: 64 k)
             if (!active || ABL(1)) continue;
             PH("ck_addr", c);
             uint32_t cbase;
@@ -1338,7 +1357,7 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
                 uint32_t all = ~0u;
                 asm volatile("" : "+s"(all));
                 const uint32_t ln = __builtin_amdgcn_mbcnt_hi(all, __builtin_amdgcn_mbcnt_lo(all, 0u));
-                cbase = lds_w(a.off_ch + ((uint32_t)wave << 8) + 4u * ln);
+                cbase = lds_w((FZ ? W::off_ch : a.off_ch) + ((uint32_t)wave << 8) + 4u * ln);
             } else {
                 cbase = gbase[c];
                 asm volatile("" : "+v"(cbase));
@@ -1356,7 +1375,7 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
                 else return LPC * m + LPC - 1 < cdm || LPC * m + cj < cdeg;
             };
             auto caddr = [&](int m) __attribute__((always_inline)) -> uint32_t {
-                return real(m) ? cbase + m * cstride : a.off_pad;
+                return real(m) ? cbase + m * cstride : (FZ ? W::off_pad : a.off_pad);
             };
             // pass 1: two minima of |V->C| and the parity of [V->C >= 0] over the lane's edges
             // (padding edges: negative, magnitude 15), then merged across the lane group
@@ -1572,7 +1591,7 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
             if (dw[0] >= DV - 1) __builtin_amdgcn_s_setprio(1);
             else __builtin_amdgcn_s_setprio(0);
         }
-        const uint32_t bslice = a.off_blut + (uint32_t)(nx * BL * 4);
+        const uint32_t bslice = (FZ ? W::off_blut : a.off_blut) + (uint32_t)(nx * BL * 4);
         if (t == a.T - 1) vn_phase(false, true, bslice, t + 1);
         else vn_phase(false, false, bslice, t + 1);
         BS_ST(2);
@@ -1698,6 +1717,7 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
 #elif defined(BS_STAMP)
     const unsigned long long npk = 1ull;
 #endif
+#undef BS_TBITS
 #undef BS_PK
 #undef BS_NEXT_PACK
 #undef BS_LANE_IS0
@@ -1711,7 +1731,7 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
         // 32-bit fields, offsets 0-1 in word 13, 2-3 in word 14
         uint32_t hw;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        const uint32_t simd = (((hw >> 4) & 3u) - reinterpret_cast<uint32_t*>(smem + a.off_red)[12]) & 3u;
+        const uint32_t simd = (((hw >> 4) & 3u) - reinterpret_cast<uint32_t*>(smem + (FZ ? W::off_red : a.off_red))[12]) & 3u;
         atomicAdd(a.stamps + 16 * wave + 13 + (simd >> 1), npk << (32 * (simd & 1)));
     }
 #endif
@@ -1724,6 +1744,8 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
 // the argument struct that kernel takes, built from this one (bs_launch_kernel).
 struct BsLaunch : BsArgsEw {
     int word;                    // BsArgsXp::word
+    bool frozen;                 // host only: the plan equals BsFrozenWman (bs_frozen_fit) and the
+                                 // request is a plain decode: launch the geometry-frozen build
 };
 
 template <class K>
@@ -1754,11 +1776,11 @@ int bs_launch_kernel(const L& a, int nblocks, int nw, size_t lds, hipStream_t s)
 // to the packs, the others exactly one per pack.  *resident (ldpc_bs.hip: one word per context and
 // build): the workgroups of this instance, workgroup size and LDS size that fit the device at
 // once, asked from the runtime when it is 0.
-template <int I, bool XP, bool Q8>
+template <int I, bool XP, bool Q8, bool FZ = false>
 int launch_bs_x(const BsLaunch& a, int npacks, int nw, size_t lds, hipStream_t s, int grid, int* resident) {
     constexpr BsInst k = kBsInst[I];
     static_assert(bs_loops(k) == (BS_LOOP_TU != 0), "BS_LOOP_TU lists the instances of bs_loops");
-    constexpr auto fn = &k_bs<k.D, k.DV, k.LPC, k.VPL, k.CPL, k.UCN, k.BIG, k.PK, k.WPE, XP, 1024, Q8>;
+    constexpr auto fn = &k_bs<k.D, k.DV, k.LPC, k.VPL, k.CPL, k.UCN, k.BIG, k.PK, k.WPE, XP, 1024, Q8, false, false, FZ>;
     int nblocks = npacks;
     if constexpr (bs_loops(k)) {
         if (grid < 0) {                      // (no LDPC_BS_GRID: the resident workgroups)
@@ -1804,7 +1826,13 @@ int launch_bs_any(const BsLaunch& a, int npacks, int nw, size_t lds, hipStream_t
                   : launch_bs_es_x<I, false, false>(a, npacks, nw, lds, s);
     } else {
         // (the generated channel comes from ldpc_decode_awgn, which exports no hard bits)
-        // (resident[0 / 1 / 2]: the decode, the hard-bit export and the in-prologue channel build)
+        // (resident[0 / 1 / 2]: the decode, the hard-bit export and the in-prologue channel build;
+        // [3 / 4]: the geometry-frozen decode and in-prologue channel builds)
+        if constexpr (I == BsFrozenWman::inst) {
+            if (a.frozen && !a.hdx)
+                return q8 ? launch_bs_x<I, false, true, true>(a, npacks, nw, lds, s, grid, resident + 4)
+                          : launch_bs_x<I, false, false, true>(a, npacks, nw, lds, s, grid, resident + 3);
+        }
         if (a.hdx) return q8 ? LDPC_ERR_UNSUPPORTED : launch_bs_x<I, true, false>(a, npacks, nw, lds, s, grid, resident + 1);
         return q8 ? launch_bs_x<I, false, true>(a, npacks, nw, lds, s, grid, resident + 2)
                   : launch_bs_x<I, false, false>(a, npacks, nw, lds, s, grid, resident);

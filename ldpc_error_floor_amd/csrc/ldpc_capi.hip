@@ -862,6 +862,11 @@ int ldpc_decode_word(ldpc_ctx* c, const float* llr_dev, int64_t B, const ldpc_de
     return decode_bs_impl(c, llr_dev, B, p, false, bs_outs(o), stream, nullptr, nullptr);
 }
 
+int ldpc_ctx_last_frozen(const ldpc_ctx* c) {
+    if (!c) return LDPC_ERR_ARG;
+    return (c->fused.bs_frozen && std::strncmp(c->last_kernel, "bsl[", 4) == 0) ? 1 : 0;
+}
+
 int ldpc_ctx_last_kernel(const ldpc_ctx* c, char* name, int32_t name_len) {
     if (!c || !name || name_len <= 0) return LDPC_ERR_ARG;
     std::strncpy(name, c->last_kernel, (size_t)name_len - 1);

@@ -19,8 +19,10 @@ struct FusedWorkspace {
     size_t bs_lut_bytes = 0;
     uint32_t* bs_bad = nullptr;    // [packs] 1: pack decoded by the v5 fixup
     int64_t bs_bad_n = 0;
-    int bs_resident[3] = {0, 0, 0};   // bit-sliced kernel with the pack loop: the workgroups resident
-    uint64_t bs_resident_key = ~0ull; // at once (decode / export / channel build), and what for
+    int bs_resident[5] = {0, 0, 0, 0, 0};   // bit-sliced kernel with the pack loop: the workgroups resident
+    uint64_t bs_resident_key = ~0ull; // at once (decode / export / channel build, the frozen decode /
+                                      // channel build), and what for
+    bool bs_frozen = false;        // the last bit-sliced decode ran a geometry-frozen build
     uint32_t* hdx = nullptr;       // [T][packs][n_vars] bit-sliced hard decisions (bit export of
     int64_t hdx_elems = 0;         // the bit-sliced kernels; fixup packs are in `hd` instead)
     bool bits_packed = false;      // the last bit-exporting decode wrote hdx (+ hd for bad packs)

@@ -437,6 +437,11 @@ class NMSDecoder:
         """The kernel that served this decoder's last decode (``ldpc_ctx_last_kernel``)."""
         return "" if self._ctx is None else self._ext.last_kernel(self._ctx)
 
+    def last_frozen(self) -> bool:
+        """Whether this decoder's last decode ran a geometry-frozen build of the bit-sliced kernel
+        (``ldpc_ctx_last_frozen``; ``LDPC_BS_FROZEN=0`` forces the generic build)."""
+        return False if self._ctx is None else bool(self._ext.last_frozen(self._ctx))
+
     def _empty_result(self, T, nt, hard, synd, counters, flags, app, iter_wrong=False):
         """An empty batch decodes to empty outputs; a caller's counters are left unchanged."""
         torch = self._torch

@@ -6,7 +6,8 @@
 
 FILE.s is a `-DBS_MARK` build of one kernel instance (hipcc --cuda-device-only -S): the kernel
 then carries ";@ph NAME.K" assembler comments at each phase start (ldpc_bs_kernel.h, PH()).
-The tool takes the depth-1 loop that holds the barriers (the T loop), builds its control-flow
+The tool takes the innermost loop that holds both barriers (the T loop: the depth-1 loop of a build
+with one pack per workgroup, a depth-2 loop inside the pack loop of the others), builds its control-flow
 graph, gives every basic block the phase of the marker last seen on the way into it (so the
 compiler's out-of-line blocks, e.g. pass 2 placed after the variable phase, keep their phase),
 and counts each VALU instruction by form, with the issue cost measured by tools/valu_rate.hip on
@@ -38,6 +39,10 @@ iteration, i.e. per pack-edge-iteration for T >> 1.
                   replayed (deal_chunks), and each marker is weighted by the slots that run it
                   (check markers K = 16 c + position, variable markers K = 10 u + edge)
   --dump P,...    the static VALU mnemonics of these phases (where the forms come from)
+  --counts        instead of the table: static counts over the T loop's blocks (the computed-call
+                  tables' entries apart) -- scalar loads by width, s_waitcnt, scratch accesses,
+                  lane moves, VALU, VALU with an SGPR operand, SALU; needs no markers, so it also
+                  takes the product build's .s
 
     python3 tools/isa_phase_table.py c4.s Li4ELb0ELi1024ELb0E --dw 1 --cwaves 1 --edges 4288 \
         --mc 16,2,2 --vchunks 8,7,7,5,5,4,4,4,3,3,3,3,3,2,1,1,1,1,1,1 \
@@ -115,31 +120,106 @@ def insts(lines):
             yield ("ins", t.split(";")[0].strip())
 
 
+def t_loop(blocks):
+    """(header, member block names) of the T loop: the innermost loop whose blocks, those of the
+    loops nested in it included, hold both barriers of an iteration.  The compiler annotates a
+    block's first lines: a loop header with "Parent Loop BBp Depth=k" for each loop around it and
+    "This [Inner ]Loop Header: Depth=d", any other block with "in Loop: Header=BBh Depth=d", h its
+    innermost loop.  A label of an inline-asm statement (the computed-call tables' .Lbpc / .Lbtab /
+    .Lbend) splits a compiler block without a note of its own: it stays in the loop of the block
+    before it."""
+    inner, parent, depth = {}, {}, {}          # block -> innermost loop; loop -> parent loop, depth
+    prev = None
+    for bn, bl in blocks:
+        if not re.match(r"^(\.LBB|%bb\.)", bn) and bn != "entry":
+            if prev in inner:
+                inner[bn] = inner[prev]
+            prev = bn
+            continue
+        prev = bn
+        note = []
+        for l in bl:                           # the label line and the comment lines under it
+            if l is not bl[0] and not l.lstrip().startswith(";"):
+                break
+            note.append(l)
+        note = " ".join(note)
+        m = re.search(r"This (?:Inner )?Loop Header: Depth=(\d+)", note)
+        if m:
+            h = bn[2:] if bn.startswith(".L") else bn
+            inner[bn], depth[h] = h, int(m.group(1))
+            ups = [(int(d), p) for p, d in re.findall(r"Parent Loop (BB\w+) Depth=(\d+)", note)]
+            parent[h] = max(ups)[1] if ups else None
+            continue
+        m = re.search(r"in Loop: Header=(BB\w+) Depth=(\d+)", note)
+        if m:
+            inner[bn] = m.group(1)
+    def inside(h, loop):                       # loop h is `loop` or nested in it
+        while h is not None and h != loop:
+            h = parent.get(h)
+        return h == loop
+    best = None
+    for loop in depth:
+        mem = [bn for bn, h in inner.items() if inside(h, loop)]
+        nbar = sum(1 for bn, bl in blocks if bn in mem for l in bl if l.split(";")[0].strip() == "s_barrier")
+        # (both barriers; a loop with one only where no loop has two)
+        key = (min(nbar, 2), depth[loop])
+        if nbar and (best is None or key > best[0]):
+            best = (key, loop, set(mem))
+    if best is None:
+        raise SystemExit("no loop with barriers")
+    return best[1], best[2]
+
+
+def loop_counts(path, want):
+    """Static counts over the T loop's blocks (the entries of the computed-call tables apart)."""
+    name, body = function_lines(open(path).read().splitlines(), want)
+    blocks = blocks_of(body)
+    tloop, members = t_loop(blocks)
+    c = defaultdict(int)
+    in_table = False
+    for bn, bl in blocks:
+        if bn.startswith(".Lbtab"):
+            in_table = True
+        elif bn.startswith(".Lbend"):
+            in_table = False
+        if bn not in members:
+            continue
+        if in_table:
+            continue
+        for kind, x in insts(bl):
+            if kind != "ins":
+                continue
+            op = x.split()[0]
+            f = classify(x)
+            if f:
+                c["VALU"] += 1
+                if f == "sgpr":
+                    c["VALU with an SGPR operand"] += 1
+                if op.startswith(("v_readlane", "v_writelane")):
+                    c[op.split("_b32")[0]] += 1
+            elif op.startswith(("s_load_", "s_buffer_load_")):
+                c["scalar loads"] += 1
+                c[op] += 1
+            elif op == "s_waitcnt":
+                c["s_waitcnt"] += 1
+            elif op.startswith("scratch_"):
+                c["scratch accesses"] += 1
+                c[op] += 1
+            elif op == "s_barrier":
+                c["s_barrier"] += 1
+            elif op.startswith("ds_"):
+                c["LDS"] += 1
+            elif op.startswith("s_") and not op.startswith("s_nop"):
+                c["SALU"] += 1
+    return name, tloop, dict(c)
+
+
 def analyse(path, want):
     lines = open(path).read().splitlines()
     name, body = function_lines(lines, want)
     blocks = blocks_of(body)
     idx = {b[0]: i for i, b in enumerate(blocks)}
-    # the T loop: the depth-1 loop whose blocks hold s_barrier
-    hdr_of = {}
-    for bn, bl in blocks:
-        head = bl[0] if bl else ""
-        m = re.search(r"Loop Header: Depth=1", head)
-        if m:
-            hdr_of[bn] = bn.lstrip(".L")
-        m = re.search(r"(?:in Loop: Header|Parent Loop) (?:=)?(BB\w+)", head) or re.search(r"Header=(BB\w+) Depth=1", head)
-        if m:
-            hdr_of[bn] = m.group(1)
-    loops = defaultdict(list)
-    for bn, h in hdr_of.items():
-        loops[h].append(bn)
-    tloop = None
-    for h, bns in loops.items():
-        if any("s_barrier" in l for bn in bns for l in blocks[idx[bn]][1]):
-            tloop = h
-    if tloop is None:
-        raise SystemExit("no loop with barriers")
-    members = set(loops[tloop])
+    tloop, members = t_loop(blocks)
     # table regions (.LbtabN .. .LbendN): jumped into by s_swappc, one entry per call
     tables = {}
     for bn, bl in blocks:
@@ -255,9 +335,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("asm")
     ap.add_argument("kernel")
-    ap.add_argument("--dw", required=True, help="per variable wave: its largest variable degree")
-    ap.add_argument("--cwaves", type=float, required=True, help="waves holding check lanes")
-    ap.add_argument("--edges", type=int, required=True, help="lifted edges")
+    ap.add_argument("--counts", action="store_true", help="static counts over the T loop instead of the table")
+    ap.add_argument("--dw", help="per variable wave: its largest variable degree")
+    ap.add_argument("--cwaves", type=float, help="waves holding check lanes")
+    ap.add_argument("--edges", type=int, help="lifted edges")
     ap.add_argument("--product", help="the product (unmarked) build's .s, for the totals")
     ap.add_argument("--alt", default="vn_beta_fix=1,vn_beta_id=0,vn_beta_sg=0,vn_beta_lds=0",
                     help="weights of the alternative paths (the share of iterations taking each)")
@@ -270,6 +351,15 @@ def main():
     ap.add_argument("--dump", help="print the static VALU mnemonics of these phases (comma list)")
     ap.add_argument("--json")
     a = ap.parse_args()
+    if a.counts:
+        name, tloop, c = loop_counts(a.asm, a.kernel)
+        print(name[:100])
+        print(f"T loop {tloop}: " + ", ".join(f"{k} {v}" for k, v in sorted(c.items())))
+        if a.json:
+            json.dump({"kernel": name, "t_loop": tloop, "counts": c}, open(a.json, "w"), indent=1)
+        return 0
+    if a.dw is None or a.cwaves is None or a.edges is None:
+        ap.error("--dw, --cwaves and --edges are required without --counts")
     alt = {kv.split("=")[0]: float(kv.split("=")[1]) for kv in a.alt.split(",") if kv}
     dw = [int(x) for x in a.dw.split(",")]
     name, counts, other, tables = analyse(a.asm, a.kernel)
