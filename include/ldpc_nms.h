@@ -300,6 +300,66 @@ int ldpc_decode_awgn_es_word(ldpc_ctx* ctx, int64_t B, const ldpc_decode_params*
    status. */
 int ldpc_es_word_supported(const ldpc_ctx* ctx, const ldpc_decode_params* params);
 
+/* Floor events (no reference counterpart): the word modes' decode with, in place
+   of a row per frame, one record per EVENT, collected on the device.  An event is a decoded frame
+   whose word -- hard_last[b] (early_stop = 0) or hard_stop[b] (early_stop = 1), as defined above --
+   is nonzero anywhere over the N*z variables, punctured and shortened bits included (a nonzero
+   syndrome implies a nonzero word, so the one test covers both).  Each event of the batch takes
+   one slot k of the caller's buffers, reserved at *ev_count:
+     ev_frame[k]   = frame_base + b, the frame's index (ldpc_decode_awgn_events: the channel's
+                     offset + b, its global codeword index; frame_base is not read there)
+     ev_info[k]    = { n_iter(b) (early_stop = 0: T),
+                       a        = the ones of the word over all N*z variables,
+                       a_target = the ones among its first target_bits (the frame's share of
+                                  counters[0]; a_target > 0 <=> the frame counts in counters[1]),
+                       b        = the ones of its syndrome over all M*z checks }
+                     -- the (a, b) signature of a trapping set; b = 0 with a > 0 is an undetected
+                     error, a wrong codeword
+     ev_word[k]    = the word, packed as a row of hard_last is: ceil(N*z/32) words, bit v % 32 of
+                     word v / 32, the bits past N*z zero; not written when ev_word is NULL
+   *ev_count accumulates over calls, as counters do, and is never zeroed by the library: it is the
+   number of events seen, the next free slot while it is below cap.  Events that would take a
+   slot >= cap are counted and not written; nothing past cap is touched.  The order of the
+   records is unspecified (sort by ev_frame on the host); all of one 32-frame pack's are adjacent.
+   counters[0..2], frame_flags, n_iter, iter_hist are exactly ldpc_decode_es's (early_stop = 1) or
+   counters and frame_flags ldpc_decode_word's (early_stop = 0; n_iter and iter_hist are then not
+   written) for the same input.  A pack of 32 codewords holding an off-grid value is not decoded
+   and is no event: frame_flags = 0x80, n_iter = 0, nothing in the counters or histogram.
+   The workspace is ldpc_decode_word's, shared with it, and B_max bytes when n_iter is NULL.
+   Served: early_stop = 0 exactly what ldpc_word_supported serves, early_stop = 1 exactly what
+   ldpc_es_word_supported serves; ldpc_decode_awgn_events serves early_stop = 1 alone, is identical
+   to ldpc_channel_awgn followed by ldpc_decode_events with frame_base = the channel's offset, and
+   generates the channel inside the kernel where ldpc_decode_awgn_es_word does.  Anything else
+   returns LDPC_ERR_UNSUPPORTED with nothing launched and nothing written.  ldpc_ctx_last_kernel
+   reports "bsl[...,events]", "bsl[...,es,events]" or "bsc[...,es,events]" (and "+gen").
+   params->outputs_size is not read.
+   size: sizeof(ldpc_event_outputs) of the caller's header; any other value -> LDPC_ERR_ARG, as are
+   a NULL ev_count, ev_frame or ev_info and a negative cap; all checked before the context is read. */
+typedef struct ldpc_event_outputs {
+    int32_t size;
+    int32_t early_stop;         /* 0: the last iteration's word, 1: the stop iteration's */
+    int64_t frame_base;         /* index of the batch's first frame */
+    int64_t cap;                /* slots of ev_frame / ev_info / ev_word, >= 0 */
+    int64_t* ev_count;          /* [1] accumulated, required */
+    int64_t* ev_frame;          /* [cap], required */
+    int32_t* ev_info;           /* [cap][4] {n_iter, a, a_target, b}, required */
+    uint32_t* ev_word;          /* [cap][ceil(N*z/32)] or NULL */
+    int64_t* counters;          /* [4], elements 0..2 accumulated, or NULL */
+    uint8_t* frame_flags;       /* [B] or NULL */
+    uint8_t* n_iter;            /* [B] or NULL (early_stop = 1) */
+    int64_t* iter_hist;         /* [T] accumulated, or NULL (early_stop = 1) */
+    uint64_t reserved1;         /* not read; pads the struct to 96 bytes */
+} ldpc_event_outputs;
+
+int ldpc_decode_events(ldpc_ctx* ctx, const float* llr_dev, int64_t B, const ldpc_decode_params* params,
+                       const ldpc_event_outputs* outputs, void* stream);
+int ldpc_decode_awgn_events(ldpc_ctx* ctx, int64_t B, const ldpc_decode_params* params,
+                            const ldpc_channel_params* channel, const ldpc_event_outputs* outputs,
+                            void* stream);
+/* Whether ldpc_decode_events with outputs->early_stop = early_stop serves these parameters on this
+   context: 1, 0, or a negative status. */
+int ldpc_events_supported(const ldpc_ctx* ctx, const ldpc_decode_params* params, int32_t early_stop);
+
 /* The LLR rows ldpc_channel_awgn(B, ..., offset) would write at batch rows idx_dev[0..n) (each
    index < B, any order), into rows_dev[n][n_vars]: the same values bit for bit, generated for
    those codewords only -- the uncorrected-word sweep regenerates the few failing frames' rows

@@ -1,11 +1,13 @@
 /*
  * ldpc_nms_debug.h — test infrastructure exported by libldpc_nms.so (not part of the decoder
- * ABI in ldpc_nms.h; host only, touches no device).
+ * ABI in ldpc_nms.h; host only and touching no device, but for ldpc_debug_events_out).
  */
 #ifndef LDPC_NMS_DEBUG_H
 #define LDPC_NMS_DEBUG_H
 
 #include <stdint.h>
+
+#include "ldpc_nms.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -46,6 +48,19 @@ int ldpc_debug_bs_frozen(const int32_t* proto, int32_t M, int32_t N, int32_t z, 
                          int32_t alpha_uniform, int32_t beta_uniform, int32_t ucn, int32_t kind,
                          float clip, int32_t* plan, int32_t* frozen, int32_t n, char* names,
                          int32_t names_len);
+
+/* The event collector of ldpc_decode_events (csrc/ldpc_events.hip, events_out) on caller-supplied
+ * device buffers instead of a decode's: planes_dev [ceil(B/32)][N*z], bit r of word (pack, v) =
+ * variable v of frame 32 pack + r (the bits of a ragged last pack's frames past B may hold
+ * anything); bad_dev [ceil(B/32)], nonzero: the pack is skipped, whatever its planes hold;
+ * n_iter_dev [B] or NULL (every record then takes T).  Of `outputs`, size, frame_base, cap and the
+ * ev_* buffers are used as ldpc_decode_events uses them and frame_flags (or NULL) takes 0x80 for
+ * the frames of skipped packs; the other fields are not read.  Launches the one kernel on
+ * `stream` on the context's device: so a test can hand it words no decode here produces (a wrong
+ * codeword: a > 0, b = 0).  Returns a status of ldpc_nms.h. */
+int ldpc_debug_events_out(ldpc_ctx* ctx, const uint32_t* planes_dev, const uint32_t* bad_dev, int64_t B,
+                          int32_t target_bits, const uint8_t* n_iter_dev, int32_t T,
+                          const ldpc_event_outputs* outputs, void* stream);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,7 @@ __all__ = [
     "DecoderWeights", "read_weight_file", "load_weights_reference_order", "expand_weights",
     "flat_weights", "create_mix_epoch", "quantize_host", "read_uncor_llr", "write_uncor_file",
     "calc_ber_fer", "Counters", "loss_forward", "NMSDecoder", "Decoder", "Session", "build_session",
-    "compute_results", "fer_sweep",
+    "compute_results", "fer_sweep", "EventBuffer", "FloorEvents", "floor_events",
 ]
 
 
@@ -32,4 +32,7 @@ def __getattr__(name):
     if name in ("compute_results", "fer_sweep"):
         from . import fer
         return getattr(fer, name)
+    if name in ("EventBuffer", "FloorEvents", "floor_events"):
+        from . import events
+        return getattr(events, name)
     raise AttributeError(name)

@@ -494,13 +494,14 @@ static Bufs make_bufs(const ldpc_ctx* c, int64_t B, const ldpc_decode_params* p)
     return b;
 }
 
-// ldpc_ctx_last_kernel's name of the decode just served: the kernel's, with ",word" inside its
-// brackets for the word modes, and "+gen" for a channel generated inside the decoding kernel (the
-// bit-sliced Q8 build or the v5 prologue), so a caller can tell it from a decode of LLRs in HBM
-static void set_last_kernel(ldpc_ctx* c, const char* kernel, bool word, bool gen) {
+// ldpc_ctx_last_kernel's name of the decode just served: the kernel's, with `mode` (",word" for the
+// word modes, ",events" for the events mode, or null) inside its brackets, and "+gen" for a channel
+// generated inside the decoding kernel (the bit-sliced Q8 build or the v5 prologue), so a caller can
+// tell it from a decode of LLRs in HBM
+static void set_last_kernel(ldpc_ctx* c, const char* kernel, const char* mode, bool gen) {
     const size_t n = std::strlen(kernel);
-    std::snprintf(c->last_kernel, sizeof(c->last_kernel), "%.*s%s%s", (int)(word && n ? n - 1 : n), kernel,
-                  word ? ",word]" : "", gen ? "+gen" : "");
+    std::snprintf(c->last_kernel, sizeof(c->last_kernel), "%.*s%s%s%s", (int)(mode && n ? n - 1 : n), kernel,
+                  mode ? mode : "", mode ? "]" : "", gen ? "+gen" : "");
 }
 
 int ldpc_awgn_in_kernel(const ldpc_ctx* c, const ldpc_decode_params* p, int32_t has_short, int32_t app) {
@@ -701,7 +702,7 @@ static int decode_impl(ldpc_ctx* c, const float* llr_dev, int64_t B, const ldpc_
     const char* served = kern == LDPC_KERNEL_FLOOD ? "flood"
                          : fl ? ffl_kernel_name(g->dev, mode, ucn, g->per_edge_w != 0)
                               : c->fused.last_kernel;
-    set_last_kernel(c, served, false, q8 || (gen && kern == LDPC_KERNEL_FUSED));
+    set_last_kernel(c, served, nullptr, q8 || (gen && kern == LDPC_KERNEL_FUSED));
 
     if (count && kern == LDPC_KERNEL_FLOOD) {
         hipLaunchKernelGGL(k_finalize, dim3(std::min(1024, (ntiles + 255) / 256)), dim3(256), 0, s, b,
@@ -776,15 +777,16 @@ struct BsOuts {
     int64_t* iter_hist;
     uint32_t* rows;
     uint8_t* word_flags;
+    const EventSink* ev;       // the events mode's sink (no rows), or null
 };
 static BsOuts bs_outs(const ldpc_es_outputs* o) {
-    return BsOuts{o->counters, o->frame_flags, o->n_iter, o->iter_hist, nullptr, nullptr};
+    return BsOuts{o->counters, o->frame_flags, o->n_iter, o->iter_hist, nullptr, nullptr, nullptr};
 }
 static BsOuts bs_outs(const ldpc_es_word_outputs* o) {
-    return BsOuts{o->counters, o->frame_flags, o->n_iter, o->iter_hist, o->hard_stop, o->word_flags};
+    return BsOuts{o->counters, o->frame_flags, o->n_iter, o->iter_hist, o->hard_stop, o->word_flags, nullptr};
 }
 static BsOuts bs_outs(const ldpc_word_outputs* o) {
-    return BsOuts{o->counters, o->frame_flags, nullptr, nullptr, o->hard_last, o->word_flags};
+    return BsOuts{o->counters, o->frame_flags, nullptr, nullptr, o->hard_last, o->word_flags, nullptr};
 }
 
 static int decode_bs_impl(ldpc_ctx* c, const float* llr_dev, int64_t B, const ldpc_decode_params* p, bool es,
@@ -804,9 +806,9 @@ static int decode_bs_impl(ldpc_ctx* c, const float* llr_dev, int64_t B, const ld
     bo.n_iter = o.n_iter;
     bo.iter_hist = o.iter_hist;
     const int st = fused_decode_bs(g->dev, b, c->fused, llr_dev, r, c->B_max, c->ntiles_max, bo, o.rows,
-                                   o.word_flags, s);
+                                   o.word_flags, s, o.ev);
     if (st != LDPC_OK) return st;
-    set_last_kernel(c, bs_kernel_name(g->dev, r), o.rows != nullptr, q8 != nullptr);
+    set_last_kernel(c, bs_kernel_name(g->dev, r), o.ev ? ",events" : o.rows ? ",word" : nullptr, q8 != nullptr);
     return hipGetLastError() == hipSuccess ? LDPC_OK : LDPC_ERR_HIP;
 }
 
@@ -860,6 +862,56 @@ int ldpc_decode_word(ldpc_ctx* c, const float* llr_dev, int64_t B, const ldpc_de
     if (!c || !llr_dev || !p || !o || o->size != (int32_t)sizeof(ldpc_word_outputs) || !o->hard_last)
         return LDPC_ERR_ARG;
     return decode_bs_impl(c, llr_dev, B, p, false, bs_outs(o), stream, nullptr, nullptr);
+}
+
+// ---- the events mode: the word modes' decode, events_out in word_out's place ----
+static_assert(sizeof(ldpc_event_outputs) == 96, "ldpc_event_outputs is part of ABI 3");
+// (the outputs' size, the required pointers and cap, checked before the context is read)
+static bool event_outputs_ok(const ldpc_event_outputs* o) {
+    return o && o->size == (int32_t)sizeof(ldpc_event_outputs) && o->ev_count && o->ev_frame && o->ev_info &&
+           o->cap >= 0;
+}
+static EventSink event_sink(const ldpc_event_outputs* o, int64_t frame_base, const ldpc_decode_params* p) {
+    return EventSink{frame_base, o->cap, o->ev_count, o->ev_frame, o->ev_info, o->ev_word, p->target_bits};
+}
+static BsOuts bs_outs(const ldpc_event_outputs* o, const EventSink* ev) {
+    const bool es = o->early_stop != 0;
+    return BsOuts{o->counters, o->frame_flags, es ? o->n_iter : nullptr, es ? o->iter_hist : nullptr, nullptr, nullptr, ev};
+}
+
+int ldpc_events_supported(const ldpc_ctx* c, const ldpc_decode_params* p, int32_t early_stop) {
+    return bs_request_supported(c, p, early_stop != 0);
+}
+
+int ldpc_decode_events(ldpc_ctx* c, const float* llr_dev, int64_t B, const ldpc_decode_params* p,
+                       const ldpc_event_outputs* o, void* stream) {
+    if (!event_outputs_ok(o)) return LDPC_ERR_ARG;
+    if (!c || !llr_dev || !p) return LDPC_ERR_ARG;
+    const EventSink ev = event_sink(o, o->frame_base, p);
+    return decode_bs_impl(c, llr_dev, B, p, o->early_stop != 0, bs_outs(o, &ev), stream, nullptr, nullptr);
+}
+
+int ldpc_decode_awgn_events(ldpc_ctx* c, int64_t B, const ldpc_decode_params* p, const ldpc_channel_params* ch,
+                            const ldpc_event_outputs* o, void* stream) {
+    if (!event_outputs_ok(o)) return LDPC_ERR_ARG;
+    if (!c || !p || !ch || !(ch->sigma > 0.0) || ch->offset < 0) return LDPC_ERR_ARG;
+    if (!o->early_stop) return LDPC_ERR_UNSUPPORTED;       // (the in-prologue channel has no full-T word build)
+    const EventSink ev = event_sink(o, ch->offset, p);
+    return decode_awgn_es_impl(c, B, p, ch, bs_outs(o, &ev), stream);
+}
+
+// (include/ldpc_nms_debug.h) events_out on the caller's planes
+int ldpc_debug_events_out(ldpc_ctx* c, const uint32_t* planes_dev, const uint32_t* bad_dev, int64_t B,
+                          int32_t target_bits, const uint8_t* n_iter_dev, int32_t T, const ldpc_event_outputs* o,
+                          void* stream) {
+    if (!event_outputs_ok(o)) return LDPC_ERR_ARG;
+    if (!c || !planes_dev || !bad_dev || B <= 0 || target_bits < 0) return LDPC_ERR_ARG;
+    ldpc_graph* g = c->g;
+    if (target_bits > g->h.N * g->h.z) return LDPC_ERR_ARG;
+    DeviceGuard dg(g->device);
+    const EventSink ev{o->frame_base, o->cap, o->ev_count, o->ev_frame, o->ev_info, o->ev_word, target_bits};
+    return events_out(g->dev, planes_dev, bad_dev, B, n_iter_dev, T, ev, o->frame_flags,
+                      reinterpret_cast<hipStream_t>(stream));
 }
 
 int ldpc_ctx_last_frozen(const ldpc_ctx* c) {

@@ -29,6 +29,8 @@ struct FusedWorkspace {
     uint32_t* hdw = nullptr;       // [ceil(B_max / 32)][n_vars] the word modes' hard decisions (last
     int64_t hdw_elems = 0;         // iteration's; stop iteration's, 3.9), bit-sliced;
                                    // allocated on first use
+    uint8_t* ev_niter = nullptr;   // [B_max] the events mode's n_iter when the caller asks for none
+    int64_t ev_niter_n = 0;        // (early stop)
     const char* last_kernel = "";  // the kernel that served the last decode (ldpc_ctx_last_kernel)
     // what the per-decode table kernels last wrote (they depend only on the graph, the weights
     // and T): a decode with the same key skips them
@@ -143,11 +145,28 @@ bool fused_awgn_v5(const DevGraph& g, int mode, int T, float clip, bool ucn, boo
 // build) stores the last (the stop) iteration's hard decisions into ws.hdw, and the output kernel
 // word_out (ldpc_word.hip) writes the rows, word_flags [B] or null (bit 0: syndrome nonzero) and,
 // for the packs the decode marked off the grid, zero rows and 0x80 in word_flags and o.flags.
+// ev: null, or the events mode's sink (ldpc_decode_events), instead of rows: the same
+// decode step into ws.hdw, then events_out (ldpc_events.hip) in word_out's place: one record per
+// frame whose word is nonzero, appended at *count (accumulated, never zeroed here): slots < cap
+// take the frame's index frame_base + b, {n_iter, a, a_target, b} and, with word, its row packed
+// as a row of `rows` is; slots >= cap are counted only.  target_bits: a_target's range.
 // Nothing is allocated or launched for a request that is not served.
 constexpr int WORD_MAX_VARS = 4096;      // (the bit-sliced plans' bound: 4 variables on 1024 lanes)
+struct EventSink {
+    int64_t frame_base, cap;
+    int64_t* count;            // [1]
+    int64_t* frame;            // [cap]
+    int32_t* info;             // [cap][4]
+    uint32_t* word;            // [cap][ceil(n_vars / 32)] or null
+    int target_bits;
+};
 bool fused_bs_supported(const DevGraph& g, const BsReq& r);
 int fused_decode_bs(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, const BsReq& r,
-                    int64_t B_max, int ntiles_max, BsOut o, uint32_t* rows, uint8_t* word_flags, hipStream_t s);
+                    int64_t B_max, int ntiles_max, BsOut o, uint32_t* rows, uint8_t* word_flags, hipStream_t s,
+                    const EventSink* ev = nullptr);
+// n_iter: [B] the early-stop decode's, or null: every record takes T
+int events_out(const DevGraph& g, const uint32_t* planes, const uint32_t* bad, int64_t B, const uint8_t* n_iter,
+               int T, const EventSink& ev, uint8_t* frame_flags, hipStream_t s);
 int word_out(const DevGraph& g, const uint32_t* planes, const uint32_t* bad, int64_t B, uint32_t* hard_last,
              uint8_t* word_flags, uint8_t* frame_flags, hipStream_t s);
 void fused_free(FusedWorkspace& ws);

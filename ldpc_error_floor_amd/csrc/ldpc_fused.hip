@@ -152,23 +152,31 @@ bool fused_bs_supported(const DevGraph& g, const BsReq& r) {
 }
 
 int fused_decode_bs(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, const BsReq& r,
-                    int64_t B_max, int ntiles_max, BsOut o, uint32_t* rows, uint8_t* word_flags, hipStream_t s) {
+                    int64_t B_max, int ntiles_max, BsOut o, uint32_t* rows, uint8_t* word_flags, hipStream_t s,
+                    const EventSink* ev) {
     // (word_out's LDS holds the 4 variables on 1024 lanes that bound every bit-sliced plan)
-    if (!fused_bs_supported(g, r) || (rows && (g.n_vars > WORD_MAX_VARS || b.B > B_max))) return LDPC_ERR_UNSUPPORTED;
+    const bool planes = rows || ev;
+    if (!fused_bs_supported(g, r) || (planes && (g.n_vars > WORD_MAX_VARS || b.B > B_max))) return LDPC_ERR_UNSUPPORTED;
     if (b.q8 && !bs_q8_ok(g, r, reinterpret_cast<const AwgnParams*>(b.gen8)->ss > 0)) return LDPC_ERR_UNSUPPORTED;
     // the word modes' scratch: one word per (pack, variable) of the largest batch, whatever T is
-    int st = rows ? dev_grow(ws.hdw, ws.hdw_elems, (size_t)((B_max + 31) / 32) * g.n_vars) : LDPC_OK;
+    int st = planes ? dev_grow(ws.hdw, ws.hdw_elems, (size_t)((B_max + 31) / 32) * g.n_vars) : LDPC_OK;
     if (st == LDPC_OK) st = ensure_bs_bad(ws, (b.B + 31) / 32, ntiles_max);
+    // (an event's record holds its n_iter: the early-stop decode writes it here when the caller takes none)
+    if (st == LDPC_OK && ev && r.es && !o.n_iter) {
+        st = dev_grow(ws.ev_niter, ws.ev_niter_n, (size_t)B_max);
+        o.n_iter = ws.ev_niter;
+    }
     if (st != LDPC_OK) return st;
     // (off-grid packs are marked -- by the kernel, in the rows by word_out --, not decoded: no v5
     // fixup, so none of its tile buffers)
     o.bad = ws.bs_bad;
-    if (rows) {
+    if (planes) {
         (r.es ? o.hdw : o.hdx) = ws.hdw;
         o.word = !r.es;
     }
     st = bs_decode(g, b, ws, llr, r, o, s);
-    if (st != LDPC_OK || !rows) return st;
+    if (st != LDPC_OK || !planes) return st;
+    if (ev) return events_out(g, ws.hdw, ws.bs_bad, b.B, r.es ? o.n_iter : nullptr, r.T, *ev, o.flags, s);
     return word_out(g, ws.hdw, ws.bs_bad, b.B, rows, word_flags, o.flags, s);
 }
 
@@ -206,6 +214,9 @@ void fused_free(FusedWorkspace& ws) {
     if (ws.hdw) (void)hipFree(ws.hdw);
     ws.hdw = nullptr;
     ws.hdw_elems = 0;
+    if (ws.ev_niter) (void)hipFree(ws.ev_niter);
+    ws.ev_niter = nullptr;
+    ws.ev_niter_n = 0;
     ws.key_gad[0] = ws.key_qtab[0] = ws.key_bslut[0] = ~0ull;
 }
 

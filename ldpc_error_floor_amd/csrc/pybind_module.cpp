@@ -10,6 +10,7 @@
 #include <string>
 
 #include "ldpc_nms.h"
+#include "ldpc_nms_debug.h"
 
 namespace py = pybind11;
 
@@ -114,6 +115,26 @@ static ldpc_es_word_outputs make_es_word_outputs(uintptr_t hard_stop, uintptr_t 
     o.size = (int32_t)sizeof(ldpc_es_word_outputs);
     o.hard_stop = reinterpret_cast<uint32_t*>(hard_stop);
     o.word_flags = reinterpret_cast<uint8_t*>(word_flags);
+    o.counters = reinterpret_cast<int64_t*>(counters);
+    o.frame_flags = reinterpret_cast<uint8_t*>(flags);
+    o.n_iter = reinterpret_cast<uint8_t*>(n_iter);
+    o.iter_hist = reinterpret_cast<int64_t*>(iter_hist);
+    return o;
+}
+
+static ldpc_event_outputs make_event_outputs(bool early_stop, int64_t frame_base, int64_t cap, uintptr_t ev_count,
+                                             uintptr_t ev_frame, uintptr_t ev_info, uintptr_t ev_word,
+                                             uintptr_t counters, uintptr_t flags, uintptr_t n_iter,
+                                             uintptr_t iter_hist) {
+    ldpc_event_outputs o{};
+    o.size = (int32_t)sizeof(ldpc_event_outputs);
+    o.early_stop = early_stop ? 1 : 0;
+    o.frame_base = frame_base;
+    o.cap = cap;
+    o.ev_count = reinterpret_cast<int64_t*>(ev_count);
+    o.ev_frame = reinterpret_cast<int64_t*>(ev_frame);
+    o.ev_info = reinterpret_cast<int32_t*>(ev_info);
+    o.ev_word = reinterpret_cast<uint32_t*>(ev_word);
     o.counters = reinterpret_cast<int64_t*>(counters);
     o.frame_flags = reinterpret_cast<uint8_t*>(flags);
     o.n_iter = reinterpret_cast<uint8_t*>(n_iter);
@@ -319,6 +340,82 @@ PYBIND11_MODULE(_ldpc_nms, m) {
         },
         py::arg("ctx"), py::arg("T"), py::arg("decoding_type"), py::arg("q_bit"),
         py::arg("target_bits"), py::arg("kernel"), py::arg("clip_llr") = 20.0f);
+    // floor events (ldpc_decode_events / ldpc_decode_awgn_events / ldpc_events_supported)
+    m.def(
+        "decode_events",
+        [](Ctx& c, uintptr_t llr, int64_t B, int T, int decoding_type, int q_bit, int target_bits,
+           float clip, int kernel, bool early_stop, int64_t frame_base, int64_t cap, uintptr_t ev_count,
+           uintptr_t ev_frame, uintptr_t ev_info, uintptr_t ev_word, uintptr_t counters, uintptr_t flags,
+           uintptr_t n_iter, uintptr_t iter_hist, uintptr_t stream) {
+            ldpc_decode_params p = make_params(T, decoding_type, q_bit, target_bits, clip, kernel);
+            ldpc_event_outputs o = make_event_outputs(early_stop, frame_base, cap, ev_count, ev_frame, ev_info,
+                                                      ev_word, counters, flags, n_iter, iter_hist);
+            int st;
+            {
+                py::gil_scoped_release nogil;
+                st = ldpc_decode_events(c.h, reinterpret_cast<const float*>(llr), B, &p, &o,
+                                        reinterpret_cast<void*>(stream));
+            }
+            check(st, "ldpc_decode_events");
+        },
+        py::arg("ctx"), py::arg("llr"), py::arg("B"), py::arg("T"), py::arg("decoding_type"),
+        py::arg("q_bit"), py::arg("target_bits"), py::arg("clip"), py::arg("kernel"),
+        py::arg("early_stop"), py::arg("frame_base"), py::arg("cap"), py::arg("ev_count"),
+        py::arg("ev_frame"), py::arg("ev_info"), py::arg("ev_word") = 0, py::arg("counters") = 0,
+        py::arg("flags") = 0, py::arg("n_iter") = 0, py::arg("iter_hist") = 0, py::arg("stream") = 0);
+    m.def(
+        "decode_awgn_events",
+        [](Ctx& c, int64_t B, int T, int decoding_type, int q_bit, int target_bits, float clip,
+           int kernel, double sigma, uint64_t seed, int64_t offset, int ps, int pe, int ss, int se,
+           bool early_stop, int64_t cap, uintptr_t ev_count, uintptr_t ev_frame, uintptr_t ev_info,
+           uintptr_t ev_word, uintptr_t counters, uintptr_t flags, uintptr_t n_iter, uintptr_t iter_hist,
+           uintptr_t stream) {
+            ldpc_decode_params p = make_params(T, decoding_type, q_bit, target_bits, clip, kernel);
+            ldpc_channel_params ch = make_channel(sigma, seed, offset, ps, pe, ss, se);
+            ldpc_event_outputs o = make_event_outputs(early_stop, 0, cap, ev_count, ev_frame, ev_info, ev_word,
+                                                      counters, flags, n_iter, iter_hist);
+            int st;
+            {
+                py::gil_scoped_release nogil;
+                st = ldpc_decode_awgn_events(c.h, B, &p, &ch, &o, reinterpret_cast<void*>(stream));
+            }
+            check(st, "ldpc_decode_awgn_events");
+        },
+        py::arg("ctx"), py::arg("B"), py::arg("T"), py::arg("decoding_type"), py::arg("q_bit"),
+        py::arg("target_bits"), py::arg("clip"), py::arg("kernel"), py::arg("sigma"),
+        py::arg("seed"), py::arg("offset"), py::arg("punct_start"), py::arg("punct_end"),
+        py::arg("short_start"), py::arg("short_end"), py::arg("early_stop"), py::arg("cap"),
+        py::arg("ev_count"), py::arg("ev_frame"), py::arg("ev_info"), py::arg("ev_word") = 0,
+        py::arg("counters") = 0, py::arg("flags") = 0, py::arg("n_iter") = 0, py::arg("iter_hist") = 0,
+        py::arg("stream") = 0);
+    m.def(
+        "events_supported",
+        [](Ctx& c, int T, int decoding_type, int q_bit, int target_bits, int kernel, float clip, bool early_stop) {
+            ldpc_decode_params p = make_params(T, decoding_type, q_bit, target_bits, clip, kernel);
+            const int st = ldpc_events_supported(c.h, &p, early_stop ? 1 : 0);
+            check(st, "ldpc_events_supported");
+            return st == 1;
+        },
+        py::arg("ctx"), py::arg("T"), py::arg("decoding_type"), py::arg("q_bit"),
+        py::arg("target_bits"), py::arg("kernel"), py::arg("clip_llr") = 20.0f, py::arg("early_stop") = false);
+    // test hook (ldpc_nms_debug.h): the event collector on caller-supplied planes
+    m.def(
+        "debug_events_out",
+        [](Ctx& c, uintptr_t planes, uintptr_t bad, int64_t B, int target_bits, uintptr_t n_iter, int T,
+           int64_t frame_base, int64_t cap, uintptr_t ev_count, uintptr_t ev_frame, uintptr_t ev_info,
+           uintptr_t ev_word, uintptr_t flags, uintptr_t stream) {
+            ldpc_event_outputs o = make_event_outputs(false, frame_base, cap, ev_count, ev_frame, ev_info, ev_word,
+                                                      0, flags, 0, 0);
+            check(ldpc_debug_events_out(c.h, reinterpret_cast<const uint32_t*>(planes),
+                                        reinterpret_cast<const uint32_t*>(bad), B, target_bits,
+                                        reinterpret_cast<const uint8_t*>(n_iter), T, &o,
+                                        reinterpret_cast<void*>(stream)),
+                  "ldpc_debug_events_out");
+        },
+        py::arg("ctx"), py::arg("planes"), py::arg("bad"), py::arg("B"), py::arg("target_bits"),
+        py::arg("n_iter"), py::arg("T"), py::arg("frame_base"), py::arg("cap"), py::arg("ev_count"),
+        py::arg("ev_frame"), py::arg("ev_info"), py::arg("ev_word") = 0, py::arg("flags") = 0,
+        py::arg("stream") = 0);
     m.def(
         "channel_awgn",
         [](uintptr_t llr, int64_t B, int n_vars, double sigma, uint64_t seed, int64_t offset,

@@ -174,6 +174,62 @@ class NMSDecoder:
         return bool(self._ext.word_supported(ctx, T, self.decoding_type, self.q_bit, self.target_bits,
                                              KERNELS[kernel or self.kernel], self.clip))
 
+    def supports_events(self, T=None, kernel=None, early_stop: bool = False) -> bool:
+        """Whether ``decode(..., events=buf)`` (``early_stop=True``: with ``early_stop=True``, and
+        ``decode_awgn(..., early_stop=True, events=buf)``) is served for this decoder
+        (``ldpc_events_supported``): exactly where ``supports_hard_last`` with the same
+        ``early_stop`` holds."""
+        T = self.T if T is None else int(T)
+        if T > self.T:
+            return False
+        ctx = self._ensure_ctx(1, T)
+        return bool(self._ext.events_supported(ctx, T, self.decoding_type, self.q_bit, self.target_bits,
+                                               KERNELS[kernel or self.kernel], self.clip, bool(early_stop)))
+
+    def _decode_events(self, llr, B, T, nt, events, frame_base, early_stop, counters, flags, n_iter, iter_hist,
+                       kernel, stream, on_off_grid, channel=None):
+        """``decode(events=...)`` and, with ``channel`` (sigma, seed, offset, punct, short) instead of
+        ``llr``, ``decode_awgn``'s: the batch's events appended to the ``EventBuffer`` beside the
+        outputs of the early-stop decode, or of the word mode without ``early_stop``."""
+        torch = self._torch
+        if on_off_grid not in ("raise", "mark"):
+            raise ValueError("on_off_grid must be 'raise' or 'mark'")
+        if events.device != self.device or events.n_vars != self.n_vars:
+            raise ValueError("events must be an EventBuffer of this decoder")
+        res = DecodeResult()
+        # (the generated channel is always on the grid)
+        check = on_off_grid == "raise" and channel is None
+        asked = flags is not None and flags is not False
+        self._es_outputs(res, B, T, counters, flags if asked else check, n_iter if early_stop else False,
+                         iter_hist if early_stop else None)
+        if B == 0:
+            return res
+        ctx = self._ensure_ctx(B, T)
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        ptr = lambda t: 0 if t is None else t.data_ptr()   # noqa: E731
+        outs = (bool(early_stop),) + (() if channel is not None else (int(frame_base),)) + (
+            events.cap, events.ev_count.data_ptr(), events.ev_frame.data_ptr(), events.ev_info.data_ptr(),
+            ptr(events.ev_word), ptr(res.counters), ptr(res.flags), ptr(res.n_iter), ptr(res.iter_hist),
+            stream.cuda_stream)
+        if channel is not None:
+            sigma, seed, offset, punct, short = channel
+            self._ext.decode_awgn_events(ctx, B, T, self.decoding_type, self.q_bit, nt, self.clip,
+                                         KERNELS[kernel or self.kernel], float(sigma), int(seed), int(offset),
+                                         int(punct[0]), int(punct[1]), int(short[0]), int(short[1]), *outs)
+            return res
+        self._ext.decode_events(ctx, llr.data_ptr(), B, T, self.decoding_type, self.q_bit, nt, self.clip,
+                                KERNELS[kernel or self.kernel], *outs)
+        if check:
+            stream.synchronize()
+            nbad = int((res.flags[:B] == 0x80).sum().item())
+            if nbad:
+                raise ValueError(f"events: {nbad} frames are in packs with LLRs off the quantizer "
+                                 "grid and were not decoded (on_off_grid='mark' returns them marked)")
+            if not asked:
+                res.flags = None
+        return res
+
     def _decode_word(self, llr, T, nt, hard_last, word_flags, counters, flags, kernel, stream, on_off_grid):
         """``decode(hard_last=...)``: the decoded words of the last iteration."""
         torch = self._torch
@@ -302,7 +358,8 @@ class NMSDecoder:
                synd: bool = False, counters=None, flags: bool = False, kernel: Optional[str] = None,
                stream=None, target_bits: Optional[int] = None, iter_wrong: bool = False,
                early_stop: bool = False, n_iter: bool = False, iter_hist=None,
-               on_off_grid: str = "raise", hard_last=False, word_flags: bool = False) -> DecodeResult:
+               on_off_grid: str = "raise", hard_last=False, word_flags: bool = False,
+               events=None, frame_base: int = 0) -> DecodeResult:
         """Decode a batch.  ``counters`` may be a caller-owned int64[4] device tensor that is
         accumulated into (``+=``); pass ``True`` to get a fresh one.  ``target_bits``
         overrides the output / FER bit range (default Nt*z).  ``iter_wrong``: the per-iteration
@@ -335,12 +392,32 @@ class NMSDecoder:
         returns -- not the last iteration's: frozen at the frame's first zero-syndrome iteration,
         iteration T - 1's for a frame that never stops.  ``word_flags`` bit 0 is then 0 for every
         frame with ``n_iter < T``; ``counters`` / ``flags`` / ``n_iter`` / ``iter_hist`` are those of
-        ``early_stop=True`` alone."""
+        ``early_stop=True`` alone.
+
+        ``events`` (an ``events.EventBuffer`` of this decoder): instead of a row per
+        frame, the batch's events -- the frames whose decoded word (the last iteration's, or with
+        ``early_stop=True`` the stop iteration's) is nonzero anywhere -- are found on the device and
+        appended to the buffer: frame index ``frame_base + b``, iterations run, ``a`` (wrong bits),
+        ``a_target`` (those among the target bits) and ``b`` (unsatisfied checks), and the word.
+        ``counters`` / ``flags`` (and ``n_iter`` / ``iter_hist`` with ``early_stop``) are those of
+        the mode without ``events``; ``hard_last`` / ``app`` / ``hard`` / ``synd`` / ``iter_wrong``
+        are not served with it and raise ``ValueError``.  Off-grid packs as above: no event."""
         torch = self._torch
         T = self.T if T is None else int(T)
         nt = self.target_bits if target_bits is None else int(target_bits)
         if T > self.T:
             raise ValueError(f"T={T} exceeds the {self.T} iterations the weights cover")
+        if events is not None:
+            bad = [k for k, v in dict(hard_last=hard_last is not False and hard_last is not None, app=app, hard=hard,
+                                      synd=synd, iter_wrong=iter_wrong, word_flags=word_flags).items() if v]
+            if not early_stop:
+                bad += [k for k, v in dict(n_iter=n_iter, iter_hist=iter_hist is not None and iter_hist is not False).items() if v]
+            if bad:
+                raise ValueError("events serves counters and flags (with early_stop: n_iter and iter_hist) only, "
+                                 "not " + ", ".join(bad))
+            llr = self._as_llr(llr)
+            return self._decode_events(llr, int(llr.shape[0]), T, nt, events, frame_base, early_stop, counters,
+                                       flags, n_iter, iter_hist, kernel, stream, on_off_grid)
         if hard_last is not False and hard_last is not None and early_stop:
             self._es_check_exports(app=app, hard=hard, synd=synd, iter_wrong=iter_wrong)
             llr = self._as_llr(llr)
@@ -468,7 +545,7 @@ class NMSDecoder:
                     T: Optional[int] = None, app: bool = False, counters=None, flags=None,
                     kernel: Optional[str] = None, stream=None, iter_wrong: bool = False,
                     early_stop: bool = False, n_iter: bool = False, iter_hist=None,
-                    hard_last=False, word_flags: bool = False) -> DecodeResult:
+                    hard_last=False, word_flags: bool = False, events=None) -> DecodeResult:
         """Decode B codewords whose LLRs come from the on-GPU AWGN channel, generated inside
         the decoder (``ldpc_decode_awgn``): identical to ``decode(awgn(...))`` without the
         LLRs ever being written to HBM.  ``counters`` / ``flags`` as in ``decode``;
@@ -477,8 +554,26 @@ class NMSDecoder:
         (each frame's word at its stop iteration, as ``decode(early_stop=True, hard_last=...)``;
         DESIGN.md 3.9).  Without ``early_stop``, ``hard_last`` is not served here (the kernels'
         in-prologue channel has no export build) and raises ``ValueError``: compose ``awgn()`` and
-        ``decode()``."""
+        ``decode()``.  ``events`` (an ``EventBuffer``) likewise needs
+        ``early_stop=True``: the batch's events are appended with the frame index ``offset + b``,
+        the codeword's global index in the channel's stream."""
         want_word = hard_last is not False and hard_last is not None
+        if events is not None:
+            if not early_stop:
+                raise ValueError("decode_awgn does not serve events without early_stop: use "
+                                 "decode(awgn(...), events=buf, frame_base=offset)")
+            bad = [k for k, v in dict(hard_last=want_word, app=app, iter_wrong=iter_wrong, word_flags=word_flags).items() if v]
+            if bad:
+                raise ValueError("events serves counters and flags (with early_stop: n_iter and iter_hist) only, "
+                                 "not " + ", ".join(bad))
+            T = self.T if T is None else int(T)
+            if T > self.T:
+                raise ValueError(f"T={T} exceeds the {self.T} iterations the weights cover")
+            punct = getattr(self, "punct", (0, 0)) if punct is None else punct
+            short = getattr(self, "short", (0, 0)) if short is None else short
+            return self._decode_events(None, int(B), T, self.target_bits, events, 0, True, counters, flags, n_iter,
+                                       iter_hist, kernel, stream, "mark",
+                                       channel=(sigma, seed, offset, punct, short))
         if want_word and not early_stop:
             raise ValueError("decode_awgn does not serve hard_last: use decode(awgn(...), hard_last=True)")
         if word_flags and not want_word:
