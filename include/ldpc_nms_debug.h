@@ -30,7 +30,13 @@ extern "C" {
  * (LDPC_BOUNDS_ES_BSC = 8): also check the compressed kernel's early-stop plan where a decode in
  * the mode would take it (no bsl plan serves the graph, uniform beta = 1: 5G BG1) -- its syndrome
  * words inside the RED region and before the alpha table, the LDS size, and the chunk, position
- * and channel-table checks of the bsc plan; one more plan in the count.  Only
+ * and channel-table checks of the bsc plan; one more plan in the count.  flags bit 4
+ * (LDPC_BOUNDS_UCN1 = 16): also check the plan of the one-chunk UCN instance that decodes without
+ * early stop take when UCN weights are set and no earlier instance serves them (wman with
+ * alpha' != alpha: the last kBsInst entry) -- with the UCN setting alone, as only such requests
+ * are planned on it: its hard decisions, its cn_hd and hard-decision-address reads and its packed
+ * alpha-table address; one more plan in the count where the graph fits it, and without the bit
+ * the plans checked and the count are those of the other instances.  Only
  * the checks read the flags, no kernel or launch path does.  Returns the number of plans
  * checked (>= 0) or a negative status; *violations = out-of-bounds reads found, msg = the
  * first one ("" if none). */

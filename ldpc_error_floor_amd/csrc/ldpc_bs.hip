@@ -219,8 +219,9 @@ static BsPlan plan_inst(const DevGraph& g, int i, bool ucn, float clip, int min_
     o += (size_t)2 * p.bcols * BLUT_W * 4;
     // 16-bit alpha-table addresses (PKG).  (The ES instances: the packed address is a check lane's
     // alpha-table base in the first buffer, the only one that has to stay below 64 KB -- wman's
-    // per-row tables of a UCN-compiled instance end above it)
-    if (k.PK && k.CPL == 1 && (k.ES ? (size_t)p.off_alut + (size_t)p.arows * LUT_W * 4 : o) > 65535) return p;
+    // per-row tables of a UCN-compiled instance end above it; kBsInstUcn1, the same geometry, alike)
+    const bool first_buffer = k.ES || i == kBsInstUcn1;
+    if (k.PK && k.CPL == 1 && (first_buffer ? (size_t)p.off_alut + (size_t)p.arows * LUT_W * 4 : o) > 65535) return p;
     if (k.CPL == 1) {                              // the check lanes' slot-base words
         p.off_ch = (uint32_t)o;
         o += (size_t)4 * 64 * p.nw;
@@ -261,6 +262,9 @@ BsPlan bs_plan(const DevGraph& g, int mode, bool ucn, bool per_edge_w, float cli
         }
         if (want_lpc != 0 && want_lpc != kBsInst[i].LPC) continue;
         if (want_inst >= 0 && want_inst != i) continue;
+        // (the last entry: requests with UCN weights that no entry before it serves -- wman with
+        // alpha' != alpha; a request without them never takes it, forced or not)
+        if (i == kBsInstUcn1 && !ucn) continue;
         BsPlan q = plan_inst(g, i, ucn, clip, min_cdeg, mode, T);
         if (q.ok) return q;
     }
@@ -1188,6 +1192,9 @@ extern "C" int ldpc_debug_bs_bounds(const int32_t* proto, int32_t M, int32_t N, 
             // (the early-stop instances' plans with LDPC_BOUNDS_ES only: without it the checked
             // plans are those of the decodes without the mode)
             if (kBsInst[i].ES && !(flags & LDPC_BOUNDS_ES)) continue;
+            // (the one-chunk UCN instance that only requests with UCN weights take, bs_plan: that
+            // plan with LDPC_BOUNDS_UCN1 only, so the count without the bit is what it was)
+            if (i == kBsInstUcn1 && (!(flags & LDPC_BOUNDS_UCN1) || u == 0)) continue;
             const BsPlan p = plan_inst(g, i, u != 0, clip, min_cdeg, mode, T);
             if (!p.ok) continue;
             const BsHostTables t = bs_host_tables(g, p);

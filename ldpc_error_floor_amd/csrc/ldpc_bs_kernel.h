@@ -69,8 +69,19 @@ constexpr BsInst kBsInst[] = {
     {10, 8, 4, 2, 3, true, true, false, 4},      // LDPC_BS_LPC=4 A/B
     {15, 6, 4, 1, 1, true, false, true, 6, true},   // wman, early stop (UCN-compiled: HD / syndromes)
     {24, 4, 4, 1, 1, true, true, true, 6, true},    // 802.11n, early stop
+    {15, 6, 4, 1, 1, true, false, true, 6},      // wman with alpha' != alpha (the boosting cascade):
+                                                 // last, and planned for UCN requests only (bs_plan)
 };
 constexpr int kBsNInst = sizeof(kBsInst) / sizeof(kBsInst[0]);
+// The one-chunk UCN instance of wman's geometry for decodes without early stop (the decode, the
+// in-prologue channel and the export / word builds; no pack loop, no frozen build).  It has the
+// degree bounds of entry 0, which comes first and serves every request without alpha', so bs_plan
+// considers it for requests with UCN weights alone, after every other entry: a request that had a
+// plan before this entry keeps that plan.
+constexpr int kBsInstUcn1 = 9;
+static_assert(kBsInstUcn1 == kBsNInst - 1 && kBsInst[kBsInstUcn1].UCN && !kBsInst[kBsInstUcn1].ES &&
+              kBsInst[kBsInstUcn1].VPL == 1 && kBsInst[kBsInstUcn1].CPL == 1 && kBsInst[kBsInstUcn1].PK,
+              "the one-chunk UCN instance is the table's last entry");
 
 // The QMS channel generated in the kernel's prologue (Q8 builds; ldpc_decode_awgn, SURVEY 8 f
 // rank 1): the byte each LLR would have on the q-bit grid (level + 16 + kmin), from the same

@@ -127,7 +127,8 @@ int bsc_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float
                const BsOut& o, hipStream_t s);
 // host-side bounds check of the bsc plan (test infrastructure, ldpc_debug_bs_bounds), and the
 // flags of that check (include/ldpc_nms_debug.h): no kernel or launch path reads them
-enum { LDPC_BOUNDS_PRE_GUARD = 1, LDPC_BOUNDS_BIG_TABLES = 2, LDPC_BOUNDS_ES = 4, LDPC_BOUNDS_ES_BSC = 8 };
+enum { LDPC_BOUNDS_PRE_GUARD = 1, LDPC_BOUNDS_BIG_TABLES = 2, LDPC_BOUNDS_ES = 4, LDPC_BOUNDS_ES_BSC = 8,
+       LDPC_BOUNDS_UCN1 = 16 };
 // (es: the graph's early-stop plan instead, LDPC_BOUNDS_ES_BSC)
 int bsc_debug_bounds(const DevGraph& g, int mode, float clip, int T, int flags, int& violations,
                      std::string& first, bool es = false);

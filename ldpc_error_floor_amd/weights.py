@@ -25,7 +25,7 @@ from typing import Dict, Optional
 import numpy as np
 
 __all__ = ["WeightFile", "read_weight_file", "load_weights_reference_order",
-           "expand_weights", "DecoderWeights", "flat_weights"]
+           "expand_weights", "DecoderWeights", "flat_weights", "weights_from_file"]
 
 
 @dataclass
@@ -195,6 +195,26 @@ def expand_weights(sharing, rows: Dict[int, np.ndarray], T: int, graph,
     return DecoderWeights(np.ascontiguousarray(alpha, np.float32),
                           None if alpha_ucn is None else np.ascontiguousarray(alpha_ucn, np.float32),
                           np.ascontiguousarray(beta, np.float32))
+
+
+def weights_from_file(path: str, sharing, graph, T: Optional[int] = None) -> DecoderWeights:
+    """The tables of a trained-weight file decoded with ``sharing`` (the tools' ``--weights FILE
+    --sharing a,b,c [--T n]``: a trained cascade -- base and post decoder in one file -- run as one
+    graph).  ``sharing`` names the kinds taken from the file, which must hold a block for each of
+    them; ``T`` defaults to the rows of the file's shortest block taken."""
+    sharing = tuple(int(x) for x in sharing)
+    if len(sharing) != 3:
+        raise ValueError(f"sharing {sharing!r}: three values (CN, UCN, VN)")
+    wf = read_weight_file(path)
+    blocks = {k: wf.blocks[k] for k in range(3) if sharing[k] > 0 and k in wf.blocks}
+    missing = [k for k in range(3) if sharing[k] > 0 and k not in blocks]
+    if missing:
+        raise ValueError(f"{path}: no block for weight kind(s) {missing} (file sharing {wf.sharing})")
+    if T is None:
+        if not blocks:
+            raise ValueError("sharing takes no weights from the file: give T")
+        T = min(b.shape[0] for b in blocks.values())
+    return expand_weights(sharing, blocks, int(T), graph)
 
 
 def flat_weights(graph, T: int, alpha: float = 1.0, beta: float = 1.0,

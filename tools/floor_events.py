@@ -6,11 +6,16 @@ and write the events (frame index, iterations, a, a_target, b, the packed words)
 
   python tools/floor_events.py --config C2|C3|C4|C5 --snr DB --n N [--batch B] [--seed S]
                                [--begin I --end J] [--full-t] [--cap K] [--no-words] [--out FILE]
+                               [--weights FILE --sharing a,b,c [--T n]]
 
   --config   one of bench.py's configs, with its weights, puncturing and shortening
   --full-t   the last iteration's word instead of the early-stop decode's word at the stop
              iteration: ``awgn()`` + ``decode()`` (the in-kernel channel has no full-T word build);
              the only mode of C4, which has no early-stop build
+  --weights  a trained-weight file decoded with --sharing (and --T iterations, default the file's
+             rows) instead of the config's weights; graph, lifting, puncturing and shortening stay
+             the config's.  A trained cascade (base and post decoder as one graph, sharing 3,3,3 or
+             2,2,2 with alpha' != alpha) on C2 runs bsl[...,ucn]; its full-T events need --full-t
   --begin/--end  a sub-range [I, J) of the N codewords; the npz files of a partition concatenate
              (``FloorEvents.concat``) to the file of the whole range
   --out      default bench_out/floor_events_<config>_<snr>dB.npz (bench_out/ is git-ignored)
@@ -33,7 +38,13 @@ def parse(argv=None):
     ap.add_argument("--cap", type=int, default=1 << 16, help="events the device buffer holds")
     ap.add_argument("--no-words", action="store_true", help="keep the weights only, not the words")
     ap.add_argument("--out", default=None)
-    return ap.parse_args(argv)
+    ap.add_argument("--weights", default=None, help="a trained-weight file instead of the config's weights")
+    ap.add_argument("--sharing", default=None, help="a,b,c: the sharing the file is decoded with")
+    ap.add_argument("--T", type=int, default=None, help="iterations (default: the file's rows)")
+    a = ap.parse_args(argv)
+    if (a.weights is None) != (a.sharing is None) or (a.T is not None and a.weights is None):
+        ap.error("--weights FILE --sharing a,b,c [--T n] go together")
+    return a
 
 
 def main(argv=None):
@@ -46,6 +57,9 @@ def main(argv=None):
         raise SystemExit(f"unknown config {a.config!r}: one of {sorted(bench.CONFIGS)}")
     cfg = bench.CONFIGS[a.config]
     proto, g, W, cp = bench.load_problem(config=a.config)
+    if a.weights:
+        from ldpc_error_floor_amd.weights import weights_from_file
+        W = weights_from_file(a.weights, a.sharing.split(","), g, a.T)
     dev = torch.device("cuda", 0)
     batch = min(a.batch, a.n)
     dec = NMSDecoder(proto, cfg["z"], W, 2, 5, device=dev, B_max=batch)

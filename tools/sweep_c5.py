@@ -28,6 +28,11 @@ block (plus a max of the stage time).
 
 ``--config C2|C3|C4`` sweeps another SURVEY §8 d workload the same way (its trained weights and
 channel ranges, bench.CONFIGS); the output is then ``<out>/sweep_<config>.json``.
+
+``--weights FILE --sharing a,b,c [--T n]`` sweeps a trained-weight file decoded with that sharing
+(``--T`` iterations, default the file's rows) instead of the config's weights; graph, lifting,
+puncturing and shortening stay the config's.  A trained cascade on C2 (base and post decoder as one
+graph, alpha' != alpha) runs ``bsl[...,ucn]``.
 """
 import argparse
 import json
@@ -58,7 +63,12 @@ def parse(argv=None):
                     help="decode with the syndrome stop rule (fer_sweep(early_stop=True): each frame's "
                          "outputs at its first zero-syndrome iteration, not the full-T numbers); "
                          "records the mean iterations and their histogram per point; not with --uncor")
+    ap.add_argument("--weights", default=None, help="a trained-weight file instead of the config's weights")
+    ap.add_argument("--sharing", default=None, help="a,b,c: the sharing the file is decoded with")
+    ap.add_argument("--T", type=int, default=None, help="iterations (default: the file's rows)")
     a = ap.parse_args(argv)
+    if (a.weights is None) != (a.sharing is None) or (a.T is not None and a.weights is None):
+        ap.error("--weights FILE --sharing a,b,c [--T n] go together")
     if a.early_stop and a.uncor:
         ap.error("--early-stop does not collect uncorrected words (--uncor)")
     if a.gpus < 1:
@@ -108,11 +118,16 @@ def main(argv=None, make_decoder=None):
     os.makedirs(a.out, exist_ok=True)
     cfg = bench.CONFIGS[a.config]
     proto, g, W, cp = bench.load_problem(config=a.config)
+    if a.weights:
+        from ldpc_error_floor_amd.weights import weights_from_file
+        W = weights_from_file(a.weights, a.sharing.split(","), g, a.T)
     if make_decoder is None:
         from ldpc_error_floor_amd.decoder import NMSDecoder
         dec = NMSDecoder(proto, cfg["z"], W, 2, 5, device=dev, B_max=a.batch)
     else:
         dec = make_decoder(a.config, dev, a.batch)
+        if a.weights:
+            dec.set_weights(W)
     dec.punct, dec.short = cfg.get("punct", (0, 0)), cfg.get("short", (0, 0))
     kernel = dec.kernel_info()[1] if hasattr(dec, "kernel_info") else type(dec).__name__
     snrs = [float(x) for x in (a.deep_snrs or a.snrs).split(",")]
@@ -176,6 +191,7 @@ def main(argv=None, make_decoder=None):
         if a.early_stop and hasattr(dec, "last_kernel"):   # (the early-stop build that served it)
             kernel = dec.last_kernel() or kernel
         out = {"workload": workload(a.config, cfg) +
+               (f"; weights replaced by {os.path.basename(a.weights)} as [{a.sharing}], T={W.T}" if a.weights else "") +
                ", on-GPU Philox AWGN (seed 1076 + 7919 x SNR in mdB, + 104729 in the deep stage, "
                "indexed by the global codeword number), all-zero codeword",
                "kernel": kernel, "n_gpus": world,
