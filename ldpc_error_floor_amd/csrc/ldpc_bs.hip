@@ -890,6 +890,18 @@ static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const Bs
     // LDPC_BS_GRID=n launches n (A/B and tests; read at every launch), 0 one per pack
     int grid = -1;
     if (const char* e = getenv("LDPC_BS_GRID")) grid = std::max(atoi(e), 0);
+    // the pack loop hands its packs out by ticket (ldpc_bs_kernel.h, BS_RED_NEXT; launch_bs_x zeroes
+    // the word before each launch that loops back); LDPC_BS_TICKETS=0, read at every launch like
+    // LDPC_BS_GRID, keeps the fixed stride
+    a.ticket = nullptr;
+    if (bs_loops(k)) {
+        const char* e = getenv("LDPC_BS_TICKETS");
+        if (e ? atoi(e) != 0 : true) {
+            if (!ws.bs_ticket && hipMalloc(reinterpret_cast<void**>(&ws.bs_ticket), sizeof(uint32_t)) != hipSuccess)
+                return LDPC_ERR_OOM;
+            a.ticket = ws.bs_ticket;
+        }
+    }
     static const auto kLaunch = launch_table(std::make_integer_sequence<int, kBsNInst>{});
     // (A/B: LDPC_BS_LDS_MIN=bytes requests at least that much dynamic LDS per workgroup, fewer
     // workgroups per CU -- the occupancy experiment; the kernel uses only its own layout)
@@ -902,9 +914,19 @@ static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const Bs
     }
 #ifdef BS_STAMP
     // diagnostic build: per-wave phase clocks of this decode, printed to stderr
+    // (behind the per-wave table: one record per workgroup, sized by the largest grid, one
+    // workgroup per pack; a launched workgroup's record has packs > 0)
     static unsigned long long* dst = nullptr;
-    if (!dst && hipMalloc(reinterpret_cast<void**>(&dst), 256 * 8) != hipSuccess) return LDPC_ERR_OOM;
-    if (hipMemsetAsync(dst, 0, 256 * 8, s) != hipSuccess) return LDPC_ERR_HIP;
+    static size_t dst_words = 0;
+    const size_t st_words = BS_WG_BASE + (size_t)BS_WG_REC * npacks;
+    if (dst_words < st_words) {
+        if (dst && (hipStreamSynchronize(s) != hipSuccess || hipFree(dst) != hipSuccess)) return LDPC_ERR_HIP;
+        dst = nullptr;
+        dst_words = 0;
+        if (hipMalloc(reinterpret_cast<void**>(&dst), st_words * 8) != hipSuccess) return LDPC_ERR_OOM;
+        dst_words = st_words;
+    }
+    if (hipMemsetAsync(dst, 0, st_words * 8, s) != hipSuccess) return LDPC_ERR_HIP;
     a.stamps = dst;
     st = kLaunch[p.inst](a, npacks, p.nw, lds, s, b.q8 != nullptr, grid, ws.bs_resident);
     unsigned long long hst[256];
@@ -921,6 +943,30 @@ static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const Bs
         for (const int i : order) fprintf(stderr, " %8.0f", hst[16 * w + i] / n);
         fprintf(stderr, "  | SIMD %5.3f %5.3f %5.3f %5.3f\n", (hst[16 * w + 13] & 0xFFFFFFFFull) / n,
                 (hst[16 * w + 13] >> 32) / n, (hst[16 * w + 14] & 0xFFFFFFFFull) / n, (hst[16 * w + 14] >> 32) / n);
+    }
+    // LDPC_BS_WG_DUMP=file: the per-workgroup records of this launch appended as text, one
+    // "bs_wg" line per workgroup (tools/wg_tail.py reads them)
+    if (const char* path = getenv("LDPC_BS_WG_DUMP")) {
+        std::vector<unsigned long long> rec((size_t)BS_WG_REC * npacks);
+        if (hipMemcpy(rec.data(), dst + BS_WG_BASE, rec.size() * 8, hipMemcpyDeviceToHost) != hipSuccess)
+            return LDPC_ERR_HIP;
+        // (tickets: what the launch did -- launch_bs_x passes the word only to a launch of fewer
+        // workgroups than packs; a launched workgroup's record has packs > 0)
+        int nwg = 0;
+        for (int w = 0; w < npacks; ++w) nwg += rec[(size_t)BS_WG_REC * w] != 0;
+        const int tickets = a.ticket != nullptr && nwg < npacks;
+        if (FILE* f = fopen(path, "a")) {
+            fprintf(f, "bs_wg_launch inst %d T %d B %lld packs %d q8 %d frozen %d tickets %d\n"
+                    "# bs_wg wg packs rt_entry rt_exit clk_entry clk_exit hw_id xcc_id   (rt: 100 MHz ticks, clk: shader clocks)\n",
+                    p.inst, b.T, (long long)b.B, npacks, b.q8 != nullptr, (int)frozen, tickets);
+            for (int w = 0; w < npacks; ++w) {
+                const unsigned long long* r = rec.data() + (size_t)BS_WG_REC * w;
+                if (!r[0]) continue;
+                fprintf(f, "bs_wg %d %llu %llu %llu %llu %llu %08llx %llu\n", w, r[0], r[1], r[2], r[3], r[4],
+                        r[5] & 0xFFFFFFFFull, r[5] >> 32);
+            }
+            fclose(f);
+        }
     }
     return st;
 #else

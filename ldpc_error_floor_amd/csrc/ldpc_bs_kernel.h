@@ -114,6 +114,8 @@ struct BsArgs {
                                  // the chunk's column when it has one (else -1)
     const int32_t* cn_chunk;     // [nw][CPL] 64-lane check chunk of each wave's group (-1 idle)
     const uint32_t* cn_hd;       // [chunks * 64][HDW] UCN: LDS byte addresses of the edges' hard decisions
+                                 // (the pack loop's units, which have no UCN: the ticket word, zero at
+                                 // the launch, or null: packs by fixed stride -- BS_RED_NEXT)
     const uint32_t* alut;        // [T][AR][LUT_W]: Q(relu(alpha m step)) for m = 0..15 (AR = arows, x2 with UCN)
     const uint32_t* blut;        // [T][bcols][BLUT_W]: |Q(beta m)| for m = 0..15 (grid units), |Q(beta cu)|
     int arows, bcols;
@@ -147,8 +149,9 @@ struct BsArgs {
                                  // phase (0 check, 1 check barrier, 2 variable, 3 variable barrier,
                                  // 4 prologue's check setup, 5 epilogue, 8 entry, 9 channel, 10 its
                                  // barrier, 11 tables, 12 first variable phase; 15 packs), timing
-                                 // diagnostics
+                                 // diagnostics; then one record of BS_WG_REC words per workgroup
 };
+constexpr int BS_WG_BASE = 256, BS_WG_REC = 8;   // (the stamp builds' per-workgroup records)
 
 // The early-stop builds' arguments (ES instances): BsArgs and what the mode adds, so the other
 // builds' kernel arguments stay as they are.
@@ -616,6 +619,18 @@ constexpr bool bs_loops(const BsInst& k) { return k.VPL == 1 && k.CPL == 1 && !k
 #else
 #define BS_LOOP_TU 0
 #endif
+// How the pack loop hands out its packs.  A workgroup's first pack is blockIdx.x; every pack's
+// prologue takes the ticket of the pack after it -- one lane's returning atomic add on the launch's
+// ticket word, issued ahead of the channel's loads (the in-prologue channel: ahead of the sampler's
+// tables) so that their round trip covers its own -- and parks gridDim.x + ticket in RED[BS_RED_NEXT]
+// once the LLRs are packed, before the channel barrier (the in-prologue channel: after the tables'
+// barrier, so the ticket is not held through the sampler); every wave reads the word in the loop
+// condition, behind the channel barrier at the least.  So a workgroup that decodes faster takes more packs: the three
+// workgroups of a CU run at different rates for the whole launch (profiles/r10), and by fixed
+// stride the launch lasted as long as the slowest.  Without a ticket word (BsArgs::cn_hd null)
+// the parked index is pack + gridDim.x, the fixed stride.  RED[8..15] are outside the per-pack
+// init (RED[12]: the stamp builds' SIMD of wave 0).
+constexpr int BS_RED_NEXT = 8;
 // what a pack (index pk) derives from the arguments alone: at the kernel's entry with one pack
 // per workgroup, at each pack's top in the pack loop.  RED: [0] wrong_t, [1] all t, [2] APP > 0,
 // [3] bits; flor: the FLORW OR words; ALUT [2][AR][LUT_W], BLUT [2][bcols][BLUT_W];
@@ -707,6 +722,16 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
     // barrier waits included (diagnostic builds only)
     uint64_t sacc[13] = {};
     uint64_t sts = __builtin_amdgcn_s_memtime();
+    // one record per workgroup behind the per-wave table (BS_WG_REC words each, at stamps +
+    // BS_WG_BASE): [0] packs run, [1] / [2] the 100 MHz constant-rate clock at entry / exit,
+    // [3] / [4] wave 0's shader clock at entry / exit, [5] XCC_ID << 32 | HW_ID of wave 0.  The
+    // entry values are stored at once, so nothing of the record is held through the T loop.
+    // Analysis: tools/wg_tail.py
+    if (a.stamps && threadIdx.x == 0) {
+        unsigned long long* rec = a.stamps + BS_WG_BASE + (size_t)BS_WG_REC * blockIdx.x;
+        rec[1] = __builtin_amdgcn_s_memrealtime();
+        rec[3] = sts;
+    }
 #define BS_ST(i)                                                                                   \
     do {                                                                                           \
         const uint64_t tn_ = __builtin_amdgcn_s_memtime();                                         \
@@ -861,8 +886,24 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
 #else
 #define BS_GEN a.gen
 #endif
+#if BS_LOOP_TU
+    // the next pack of this workgroup (lane 0 of the workgroup alone; BS_RED_NEXT)
+    unsigned next_pack = pack + gridDim.x;
+    auto take_ticket = [&]() __attribute__((always_inline)) {
+        typedef __attribute__((address_space(1))) uint32_t GlobalW;
+        GlobalW* tk = (GlobalW*)(uintptr_t)a.cn_hd;
+        if (tid == 0 && tk)
+            next_pack = gridDim.x + __hip_atomic_fetch_add(tk, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    if constexpr (Q8) take_ticket();
+#endif
     if constexpr (Q8) gen_tables(BS_GEN, tid, NT);
     if (Q8 || !EBR) __syncthreads();
+#if BS_LOOP_TU
+    if constexpr (Q8) {
+        if (tid == 0) RED[BS_RED_NEXT] = next_pack;
+    }
+#endif
     BS_ST(8);
     uint32_t cs[VPL], cm[VPL][4], bg[VPL];
     int off = 0;
@@ -913,6 +954,9 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
             }
         }
     } else {
+#if BS_LOOP_TU
+    take_ticket();
+#endif
     if (var_of(0) >= 0 && !ABL(32)) {
 #pragma unroll
         for (int r = 0; r < PACK; ++r) xv[0][r] = llr_at(r, var_of(0));
@@ -942,6 +986,10 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
             for (int r = 0; r < PACK; ++r) xv[u1][r] = llr_at(r, vn);
         }
     }
+#if BS_LOOP_TU
+    // (after the channel's packing: the LLRs' round trip and their conversion cover the ticket's)
+    if (tid == 0) RED[BS_RED_NEXT] = next_pack;
+#endif
     }
     if (off) atomicOr(&RED[7], 1u);
     BS_ST(9);
@@ -1724,7 +1772,9 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
 #ifdef BS_STAMP
     ++npk;
 #endif
-    } while ((pack += gridDim.x) < (unsigned)((a.B + PACK - 1) / PACK));
+    } while ((pack = (unsigned)__builtin_amdgcn_readfirstlane(
+                  (int)reinterpret_cast<volatile uint32_t*>(smem + (FZ ? W::off_red : a.off_red))[BS_RED_NEXT])) <
+             (unsigned)((a.B + PACK - 1) / PACK));
 #elif defined(BS_STAMP)
     const unsigned long long npk = 1ull;
 #endif
@@ -1744,6 +1794,15 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
         const uint32_t simd = (((hw >> 4) & 3u) - reinterpret_cast<uint32_t*>(smem + (FZ ? W::off_red : a.off_red))[12]) & 3u;
         atomicAdd(a.stamps + 16 * wave + 13 + (simd >> 1), npk << (32 * (simd & 1)));
+        if (wave == 0) {
+            uint32_t xcc;
+            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+            unsigned long long* rec = a.stamps + BS_WG_BASE + (size_t)BS_WG_REC * blockIdx.x;
+            rec[0] = npk;
+            rec[2] = __builtin_amdgcn_s_memrealtime();
+            rec[4] = __builtin_amdgcn_s_memtime();
+            rec[5] = (unsigned long long)xcc << 32 | hw;
+        }
     }
 #endif
 #undef BS_ST
@@ -1757,6 +1816,8 @@ struct BsLaunch : BsArgsEw {
     int word;                    // BsArgsXp::word
     bool frozen;                 // host only: the plan equals BsFrozenWman (bs_frozen_fit) and the
                                  // request is a plain decode: launch the geometry-frozen build
+    uint32_t* ticket;            // host only: the pack loop's ticket word (launch_bs_x), or null:
+                                 // fixed stride (LDPC_BS_TICKETS=0)
 };
 
 template <class K>
@@ -1811,6 +1872,13 @@ int launch_bs_x(const BsLaunch& a, int npacks, int nw, size_t lds, hipStream_t s
             grid = *resident;
         }
         if (grid > 0 && grid < npacks) nblocks = grid;
+        // the packs past the first of each workgroup go by ticket (BS_RED_NEXT): the word is zeroed
+        // on the stream before every launch that loops back -- not left at zero by the kernel, so
+        // that a launch that died cannot make the next one skip packs
+        BsLaunch t = a;
+        t.cn_hd = nblocks < npacks ? a.ticket : nullptr;
+        if (t.cn_hd && hipMemsetAsync(a.ticket, 0, sizeof(uint32_t), s) != hipSuccess) return LDPC_ERR_HIP;
+        return bs_launch_kernel<fn>(t, nblocks, nw, lds, s);
     }
     return bs_launch_kernel<fn>(a, nblocks, nw, lds, s);
 }

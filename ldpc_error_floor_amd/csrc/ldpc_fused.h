@@ -22,6 +22,8 @@ struct FusedWorkspace {
     int bs_resident[5] = {0, 0, 0, 0, 0};   // bit-sliced kernel with the pack loop: the workgroups resident
     uint64_t bs_resident_key = ~0ull; // at once (decode / export / channel build, the frozen decode /
                                       // channel build), and what for
+    uint32_t* bs_ticket = nullptr; // the pack loop's ticket word (ldpc_bs_kernel.h, BS_RED_NEXT): allocated
+                                   // at the first launch that wants it, zeroed before each one
     bool bs_frozen = false;        // the last bit-sliced decode ran a geometry-frozen build
     uint32_t* hdx = nullptr;       // [T][packs][n_vars] bit-sliced hard decisions (bit export of
     int64_t hdx_elems = 0;         // the bit-sliced kernels; fixup packs are in `hd` instead)

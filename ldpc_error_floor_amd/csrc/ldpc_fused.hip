@@ -207,6 +207,8 @@ void fused_free(FusedWorkspace& ws) {
     if (ws.bs_bad) (void)hipFree(ws.bs_bad);
     ws.bs_bad = nullptr;
     ws.bs_bad_n = 0;
+    if (ws.bs_ticket) (void)hipFree(ws.bs_ticket);
+    ws.bs_ticket = nullptr;
     if (ws.hdx) (void)hipFree(ws.hdx);
     ws.hdx = nullptr;
     ws.hdx_elems = 0;
