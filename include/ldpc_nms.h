@@ -360,6 +360,47 @@ int ldpc_decode_awgn_events(ldpc_ctx* ctx, int64_t B, const ldpc_decode_params* 
    context: 1, 0, or a negative status. */
 int ldpc_events_supported(const ldpc_ctx* ctx, const ldpc_decode_params* params, int32_t early_stop);
 
+/* int8 quantized LLRs (no reference counterpart): the decodes above of LLRs that
+   are already on the quantizer grid, one byte per LLR instead of four.
+     q8_dev   device int8 [B][N*z], row-major, any alignment: g = LLR / step in grid units,
+              step 0.5 / 1 / 1 / 2 and qmax 15 / 15 / 7 / 3 for q_bit 5 / -5 / 4 / 3
+              -qmax <= g <= qmax   LLR g * step
+              -128 / +127          LLR -clip_llr / +clip_llr (a shortened bit), where the kernel
+                                   decodes shortened bits (ldpc_q8_supported with has_short = 1)
+              every other byte is invalid (so is a marker where has_short = 1 is not served)
+   For valid input every output equals, bit for bit, that of ldpc_decode / ldpc_decode_word on the
+   float LLRs the bytes stand for.  A pack of 32 codewords (b / 32) holding an invalid byte in one
+   of its codewords is not decoded: frame_flags = 0x80 (word_flags = 0x80, hard_last rows zero),
+   nothing in the counters or in iter_wrong; there is no fixup launch.
+   ldpc_decode_q8: outputs->counters / frame_flags / iter_wrong (params->outputs_size as for
+   ldpc_decode); app_all, hard_bits and synd_bits must be NULL.  ldpc_decode_q8_word:
+   ldpc_decode_word's outputs.  A NULL q8_dev, a wrong struct size or such an export pointer is
+   LDPC_ERR_ARG before the context is read.
+   Served exactly where the bit-sliced kernels serve the float request of the same kind (the
+   counters-only ldpc_decode, ldpc_decode_word) on the instances a plan takes by default; anything
+   else is LDPC_ERR_UNSUPPORTED with nothing launched or written.  ldpc_ctx_last_kernel reports
+   "bsl[...]+q8", "bsl[...,word]+q8" or "bsc[...]+q8". */
+int ldpc_decode_q8(ldpc_ctx* ctx, const int8_t* q8_dev, int64_t B, const ldpc_decode_params* params,
+                   const ldpc_decode_outputs* outputs, void* stream);
+int ldpc_decode_q8_word(ldpc_ctx* ctx, const int8_t* q8_dev, int64_t B, const ldpc_decode_params* params,
+                        const ldpc_word_outputs* word_outputs, void* stream);
+/* Whether ldpc_decode_q8 (word = 0) or ldpc_decode_q8_word (word = 1) serves these parameters on
+   this context, for input with (has_short = 1) or without the +-clip markers: 1, 0, or a negative
+   status. */
+int ldpc_q8_supported(const ldpc_ctx* ctx, const ldpc_decode_params* params, int32_t has_short,
+                      int32_t word);
+/* ldpc_channel_awgn's QMS channel as int8 rows (q8_dev [B][n_vars]): the same Philox stream and
+   level sampler, so the bytes equal ldpc_llr_to_q8 of ldpc_channel_awgn's output; punctured bits
+   0, shortened bits -128.  QMS with q_bit 5, -5, 4 or 3 only (else LDPC_ERR_UNSUPPORTED). */
+int ldpc_channel_awgn_q8(int8_t* q8_dev, int64_t B, int32_t n_vars, double sigma, uint64_t seed,
+                         int64_t offset, int32_t q_bit, int32_t punct_start, int32_t punct_end,
+                         int32_t short_start, int32_t short_end, void* stream);
+/* q8_dev[i] = the byte of llr_dev[i] on q_bit's grid for i < n: rint(llr / step) where that is
+   exact and within +-qmax, -128 / +127 for -clip_llr / +clip_llr otherwise; any other value is
+   stored saturated and counted in *n_invalid_dev (int64, zeroed by the call; may be NULL). */
+int ldpc_llr_to_q8(const float* llr_dev, int64_t n, int32_t q_bit, float clip_llr, int8_t* q8_dev,
+                   int64_t* n_invalid_dev, void* stream);
+
 /* The LLR rows ldpc_channel_awgn(B, ..., offset) would write at batch rows idx_dev[0..n) (each
    index < B, any order), into rows_dev[n][n_vars]: the same values bit for bit, generated for
    those codewords only -- the uncorrected-word sweep regenerates the few failing frames' rows

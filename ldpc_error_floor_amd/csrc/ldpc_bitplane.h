@@ -171,5 +171,34 @@ LDPC_BP_FN uint32_t tr32_step(uint32_t x, uint32_t y, int j, bool hi) {
     return hi ? (((y >> j) & m) | (x & ~m)) : ((x & m) | ((y & m) << j));
 }
 
+// ---- int8 quantized LLRs (the q8 input) -----------------------------------------
+// Four rows of one variable in a word w, one signed byte g = LLR / step each.  Returns the bytes
+// pack_bytes takes: g + 16 where -qmax <= g <= qmax; with `big` (the instance decodes shortened
+// bits) the markers -128 -> 48 - qmax and +127 -> 48 + qmax.  inv: 0x80 in the lane of every other
+// byte (its output byte is unspecified).  Byte-wise arithmetic on the whole word: a lane's sum
+// stays below 256 wherever lanes are added, so no carry crosses a lane.
+LDPC_BP_FN uint32_t l8_bytes(uint32_t w, int qmax, bool big, uint32_t& inv) {
+    constexpr uint32_t L7 = 0x7F7F7F7Fu, H = 0x80808080u, ONE = 0x01010101u;
+    const uint32_t lo = w & L7, hb = w & H;
+    uint32_t k = (lo + 16u * ONE) ^ hb;                              // (g + 16) mod 256
+    const uint32_t m = (lo + (uint32_t)qmax * ONE) ^ hb;             // (g + qmax) mod 256
+    // m > 2 qmax: m >= 128, or the low 7 bits plus 127 - 2 qmax reach 128
+    uint32_t bad = (((m & L7) + (uint32_t)(127 - 2 * qmax) * ONE) | m) & H;
+    if (big) {
+        const uint32_t yn = w ^ H, yp = w ^ L7;                      // a zero lane: -128 / +127
+        const uint32_t zn = ~(((yn & L7) + L7) | yn) & H, zp = ~(((yp & L7) + L7) | yp) & H;
+        const uint32_t mn = (zn >> 7) * 0xFFu, mp = (zp >> 7) * 0xFFu;
+        k = (k & ~(mn | mp)) | (mn & ((uint32_t)(48 - qmax) * ONE)) | (mp & ((uint32_t)(48 + qmax) * ONE));
+        bad &= ~(zn | zp);
+    }
+    inv = bad;
+    return k;
+}
+// the lanes of l8_bytes' inv for the rows set in valid4 (bit i: row i of the word): nonzero when a
+// row of the pack's codewords holds an invalid byte
+LDPC_BP_FN uint32_t l8_invalid(uint32_t inv, uint32_t valid4) {
+    return inv & (((valid4 & 15u) * 0x00204081u & 0x01010101u) << 7);
+}
+
 }  // namespace bs
 }  // namespace ldpc

@@ -63,7 +63,7 @@ __global__ void k_bs_tables(const float* __restrict__ alpha, const float* __rest
 }
 
 // ---- host: planning, graph tables, launch -------------------------------------------------
-typedef int (*LaunchFn)(const BsLaunch&, int, int, size_t, hipStream_t, bool, int, int*);
+typedef int (*LaunchFn)(const BsLaunch&, int, int, size_t, hipStream_t, int, int, int*);
 template <int... I>
 constexpr auto launch_table(std::integer_sequence<int, I...>) {
     return std::array<LaunchFn, sizeof...(I)>{&bs_launch<I>...};
@@ -302,7 +302,7 @@ static BsGeoFields bs_frozen_fields() {
 static bool bs_frozen_fit(const DevGraph& g, BsPlan& p, const BsReq& r, bool exports) {
     const char* e = getenv("LDPC_BS_FROZEN");
     if (e && atoi(e) == 0) return false;
-    if (!p.ok || p.inst != BsFrozenWman::inst || p.ucn || r.es || exports || r.T > BsFrozenWman::T_CAP) return false;
+    if (!p.ok || p.inst != BsFrozenWman::inst || p.ucn || r.es || r.l8 || exports || r.T > BsFrozenWman::T_CAP) return false;
     BsPlan q = p;
     const uint32_t d = (uint32_t)(((4 * BsFrozenWman::T_CAP + 15) & ~15) - ((4 * r.T + 15) & ~15));
     q.off_alut += d;
@@ -798,6 +798,14 @@ bool bs_q8_ok(const DevGraph& g, const BsReq& r, bool has_short) {
     return (!has_short || p.cu > 0.f) && q8_tab_fits(p);
 }
 
+bool bs_l8_ok(const DevGraph& g, const BsReq& r, bool has_short) {
+    bool to_bsc;
+    if (r.es) return false;
+    const BsPlan p = bs_route(g, r, &to_bsc);
+    if (!p.ok) return to_bsc && bsc_l8_ok(g, r, has_short);
+    return bs_l8_inst(p.inst) && (!has_short || (kBsInst[p.inst].BIG && p.cu > 0.f));
+}
+
 const char* bs_kernel_name(const DevGraph& g, const BsReq& r) {
     static thread_local char buf[64];
     bool to_bsc;
@@ -835,7 +843,9 @@ static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const Bs
     a.hdw = o.hdw;
     a.word = o.word ? 1 : 0;
     a.frozen = frozen;
-    a.llr = llr;
+    // (int8 LLRs: the L8 builds read the bytes behind the same argument)
+    a.llr = r.l8 ? reinterpret_cast<const float*>(r.l8) : llr;
+    const int src = r.l8 ? BS_SRC_L8 : b.q8 ? BS_SRC_GEN : BS_SRC_LLR;
     a.gen = bs_gen(b, q8_tab_lds(p));    // the in-prologue channel (ldpc_decode_awgn)
     a.B = b.B;
     a.n_vars = g.n_vars;
@@ -910,7 +920,7 @@ static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const Bs
     const uint64_t rkey = (uint64_t)p.inst << 48 | (uint64_t)p.nw << 32 | (uint64_t)lds;
     if (ws.bs_resident_key != rkey) {
         ws.bs_resident_key = rkey;
-        std::fill(ws.bs_resident, ws.bs_resident + 5, 0);
+        std::fill(ws.bs_resident, ws.bs_resident + 7, 0);
     }
 #ifdef BS_STAMP
     // diagnostic build: per-wave phase clocks of this decode, printed to stderr
@@ -928,7 +938,7 @@ static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const Bs
     }
     if (hipMemsetAsync(dst, 0, st_words * 8, s) != hipSuccess) return LDPC_ERR_HIP;
     a.stamps = dst;
-    st = kLaunch[p.inst](a, npacks, p.nw, lds, s, b.q8 != nullptr, grid, ws.bs_resident);
+    st = kLaunch[p.inst](a, npacks, p.nw, lds, s, src, grid, ws.bs_resident);
     unsigned long long hst[256];
     if (st != LDPC_OK || hipMemcpyAsync(hst, dst, sizeof(hst), hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
@@ -970,7 +980,7 @@ static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const Bs
     }
     return st;
 #else
-    return kLaunch[p.inst](a, npacks, p.nw, lds, s, b.q8 != nullptr, grid, ws.bs_resident);
+    return kLaunch[p.inst](a, npacks, p.nw, lds, s, src, grid, ws.bs_resident);
 #endif
 }
 

@@ -11,9 +11,9 @@ namespace ldpc {
 namespace bs {
 
 template <>
-int bs_launch<BS_INST>(const BsLaunch& a, int npacks, int nw, size_t lds, hipStream_t s, bool q8, int grid,
+int bs_launch<BS_INST>(const BsLaunch& a, int npacks, int nw, size_t lds, hipStream_t s, int src, int grid,
                        int* resident) {
-    return launch_bs_any<BS_INST>(a, npacks, nw, lds, s, q8, grid, resident);
+    return launch_bs_any<BS_INST>(a, npacks, nw, lds, s, src, grid, resident);
 }
 
 }  // namespace bs

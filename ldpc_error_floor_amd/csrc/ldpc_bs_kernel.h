@@ -662,18 +662,21 @@ constexpr int BS_RED_NEXT = 8;
 // spills 5 -> 9 VGPRs)
 // EW: the early-stop build that also keeps each codeword's hard decisions at its stop iteration
 // (DESIGN 3.9): a build of its own beside the ES build, which stays as it is.
+// L8: the LLRs read as int8 grid values (a.llr points at bytes: ldpc_decode_q8), a
+// build of its own for the reason Q8 is one; a pack with an invalid byte is marked, never fixed up
 // ES: the early-stop build (one-chunk UCN-compiled instances, one pack per
 // workgroup).  The hard decisions go to HD and the check phases take their syndromes at every
 // iteration; a pack leaves the T loop once each of its codewords has had a zero syndrome, and the
 // epilogue takes every codeword's outputs at its own first zero-syndrome iteration.
 template <int D, int DV, int LPC, int VPL, int CPL, bool UCN, bool BIG, bool PK, int WPE, bool XP, int LB, bool Q8,
-          bool ES = false, bool EW = false, bool FZ = false>
+          bool ES = false, bool EW = false, bool FZ = false, bool L8 = false>
 __global__ void __launch_bounds__(LB) __attribute__((amdgpu_waves_per_eu(WPE)))
 k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::conditional_t<XP, BsArgsXp, BsArgs>> a) {
     static_assert(LPC == 2 || LPC == 4, "lanes per check");
     using KArgs = std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::conditional_t<XP, BsArgsXp, BsArgs>>;
     static_assert(!ES || (UCN && VPL == 1 && CPL == 1 && !XP), "early stop: one-chunk UCN-compiled instances");
     static_assert(!EW || ES, "the stop-iteration word: early-stop builds");
+    static_assert(!L8 || (!Q8 && !ES && !FZ), "int8 LLRs: the decode and export builds");
     // FZ: the geometry-frozen build (ldpc_bs_frozen.h): the pack geometry is W's literals instead
     // of kernel arguments, (FZ ? W::x : a.x) at each read -- written out, not behind an accessor:
     // through one the other builds' code changed; the pack-loop decode and in-prologue channel
@@ -953,6 +956,66 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
                 pack_bytes<BIG>(Dq, valid, cs[u], cm[u], bg[u]);
             }
         }
+    } else if constexpr (L8) {
+        // int8 LLRs (ldpc_decode_q8): the float path's steps on bytes -- the same descriptor over the
+        // pack's valid rows (one byte per LLR), the lane's v in voffset and the row's r nv in soffset
+        // -- a row past the batch takes the last valid row's offset, a scalar min, so no load leaves
+        // the pack's rows whatever the range check does with soffset, and pack_bytes masks its bits
+        // as it masks the zeros the float path reads there; four rows per word, converted to the
+        // bytes pack_bytes takes (ldpc_bitplane.h, l8_bytes).  An invalid byte in a row of the pack
+        // raises the flag that sends a float pack to the fixup; here the pack is marked instead.
+#if BS_LOOP_TU
+        take_ticket();
+#endif
+        const __amdgpu_buffer_rsrc_t l8_rs = __builtin_amdgcn_make_buffer_rsrc(
+            (void*)(reinterpret_cast<const uint8_t*>(a.llr) + b0 * nv), 0, nvalid * nv, 0x00020000);
+        auto l8_load = [&](uint32_t (&Dw)[8], int v) __attribute__((always_inline)) {
+            uint32_t by[PACK];
+#pragma unroll
+            for (int r = 0; r < PACK; ++r)
+                by[r] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(l8_rs, v, min(r, nvalid - 1) * nv, 0);
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+                Dw[i] = by[4 * i] | by[4 * i + 1] << 8 | by[4 * i + 2] << 16 | by[4 * i + 3] << 24;
+        };
+        // (pack loop: defined on every path, as xv is)
+        uint32_t Dw[VPL][8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) Dw[0][i] = 0u;
+        if (var_of(0) >= 0 && !ABL(32)) l8_load(Dw[0], var_of(0));
+        if (EBR) {
+            asm volatile("" ::: "memory");
+            __builtin_amdgcn_s_waitcnt(0xC07F);          // lgkmcnt(0), vmcnt / expcnt untouched
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+        }
+        const bool l8_big = BIG && a.cu > 0.f;
+        uint32_t l8_bad = 0u;
+#pragma unroll
+        for (int u = 0; u < VPL; ++u) {
+            cs[u] = 0u;
+            bg[u] = 0u;
+#pragma unroll
+            for (int p = 0; p < 4; ++p) cm[u][p] = 0u;
+            const int v = var_of(u);
+            const int u1 = u + 1 < VPL ? u + 1 : u;
+            const int vn = (u + 1 < VPL && !ABL(32)) ? var_of(u1) : -1;
+            if (v >= 0 && !ABL(32)) {
+                uint32_t Dk[8];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    uint32_t iv;
+                    Dk[i] = l8_bytes(Dw[u][i], a.qmax, l8_big, iv);
+                    l8_bad |= l8_invalid(iv, valid >> (4 * i));
+                }
+                pack_bytes<BIG>(Dk, valid, cs[u], cm[u], bg[u]);
+            }
+            if (vn >= 0) l8_load(Dw[u1], vn);
+        }
+        off = l8_bad != 0u;
+#if BS_LOOP_TU
+        if (tid == 0) RED[BS_RED_NEXT] = next_pack;
+#endif
     } else {
 #if BS_LOOP_TU
     take_ticket();
@@ -1003,6 +1066,10 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
                 if (a.flags) a.flags[b0 + tid] = 0x80;
                 if (kern_args<KArgs>().n_iter) kern_args<KArgs>().n_iter[b0 + tid] = 0;
             }
+        }
+        if constexpr (L8) {
+            // int8 LLRs: an invalid byte has no float decode to fall back to; marked the same way
+            if (tid < nvalid && a.flags) a.flags[b0 + tid] = 0x80;
         }
         if (tid == 0) a.bad[BS_PK] = 1u;
         BS_NEXT_PACK;                          // (wave-uniform: every thread read the same word)
@@ -1848,11 +1915,11 @@ int bs_launch_kernel(const L& a, int nblocks, int nw, size_t lds, hipStream_t s)
 // to the packs, the others exactly one per pack.  *resident (ldpc_bs.hip: one word per context and
 // build): the workgroups of this instance, workgroup size and LDS size that fit the device at
 // once, asked from the runtime when it is 0.
-template <int I, bool XP, bool Q8, bool FZ = false>
+template <int I, bool XP, bool Q8, bool FZ = false, bool L8 = false>
 int launch_bs_x(const BsLaunch& a, int npacks, int nw, size_t lds, hipStream_t s, int grid, int* resident) {
     constexpr BsInst k = kBsInst[I];
     static_assert(bs_loops(k) == (BS_LOOP_TU != 0), "BS_LOOP_TU lists the instances of bs_loops");
-    constexpr auto fn = &k_bs<k.D, k.DV, k.LPC, k.VPL, k.CPL, k.UCN, k.BIG, k.PK, k.WPE, XP, 1024, Q8, false, false, FZ>;
+    constexpr auto fn = &k_bs<k.D, k.DV, k.LPC, k.VPL, k.CPL, k.UCN, k.BIG, k.PK, k.WPE, XP, 1024, Q8, false, false, FZ, L8>;
     int nblocks = npacks;
     if constexpr (bs_loops(k)) {
         if (grid < 0) {                      // (no LDPC_BS_GRID: the resident workgroups)
@@ -1894,8 +1961,23 @@ int launch_bs_es_x(const BsLaunch& a, int npacks, int nw, size_t lds, hipStream_
 }
 // instance I's launch: an ES instance has the early-stop builds alone (with a plane buffer for the
 // stop-iteration words, the EW build: DESIGN 3.9); the others never see the early-stop arguments
+// The instances with the int8-LLR builds (L8): every one a plan takes by default for a decode
+// without early stop; the A/B-only entries (2, 6) and the early-stop ones have none.
+constexpr bool bs_l8_inst(int i) { return i == 0 || i == 1 || i == 3 || i == 4 || i == 5 || i == kBsInstUcn1; }
+// the channel a launch decodes: float LLRs, the in-prologue generator (Q8 builds) or int8 LLRs (L8)
+enum BsSrc { BS_SRC_LLR = 0, BS_SRC_GEN = 1, BS_SRC_L8 = 2 };
 template <int I>
-int launch_bs_any(const BsLaunch& a, int npacks, int nw, size_t lds, hipStream_t s, bool q8, int grid, int* resident) {
+int launch_bs_any(const BsLaunch& a, int npacks, int nw, size_t lds, hipStream_t s, int src, int grid, int* resident) {
+    const bool q8 = src == BS_SRC_GEN;
+    if (src == BS_SRC_L8) {
+        // (resident[5 / 6]: the int8 decode and word builds; the word mode alone exports: hdx with word)
+        if constexpr (bs_l8_inst(I)) {
+            if (a.hdw || (a.hdx && !a.word)) return LDPC_ERR_UNSUPPORTED;
+            return a.hdx ? launch_bs_x<I, true, false, false, true>(a, npacks, nw, lds, s, grid, resident + 6)
+                         : launch_bs_x<I, false, false, false, true>(a, npacks, nw, lds, s, grid, resident + 5);
+        }
+        return LDPC_ERR_UNSUPPORTED;
+    }
     if constexpr (kBsInst[I].ES) {
         if (a.hdx) return LDPC_ERR_UNSUPPORTED;
         if (a.hdw)
@@ -1920,7 +2002,7 @@ int launch_bs_any(const BsLaunch& a, int npacks, int nw, size_t lds, hipStream_t
 
 // per-instance translation units (ldpc_bs_inst.hip, -DBS_INST=i)
 template <int I>
-int bs_launch(const BsLaunch& a, int npacks, int nw, size_t lds, hipStream_t s, bool q8, int grid, int* resident);
+int bs_launch(const BsLaunch& a, int npacks, int nw, size_t lds, hipStream_t s, int src, int grid, int* resident);
 
 }  // namespace bs
 }  // namespace ldpc

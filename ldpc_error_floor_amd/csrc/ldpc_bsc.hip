@@ -129,12 +129,14 @@ __device__ __forceinline__ void lds_dput(uint32_t addr, uint32_t x, uint32_t y) 
 // variable ORs into the pack's row in global memory: zero at the start, hd_t & nn on the few
 // iterations where codewords stop, hd_{T-1} & ~done in the last variable phase.  The ORs are
 // atomics without a return value, so no wave waits for memory inside the loop.
+// L8: the LLRs read as int8 grid values (a.llr points at bytes; as bsl's L8 build)
 template <int D, int DVH, int DVL, int LPC, int VPL, int CPL, int WPE, bool XP, int LB, bool MIX, bool B1, bool Q8,
-          bool ES = false, bool EW = false>
+          bool ES = false, bool EW = false, bool L8 = false>
 __global__ void __launch_bounds__(LB) __attribute__((amdgpu_waves_per_eu(WPE)))
 k_bsc(std::conditional_t<ES, std::conditional_t<EW, BscArgsEw, BscArgsEs>, std::conditional_t<XP, BscArgsXp, BscArgs>> a) {
     static_assert(!ES || (B1 && !XP), "early stop: the beta = 1 build, no export");
     static_assert(!EW || ES, "the stop-iteration word: early-stop builds");
+    static_assert(!L8 || (!Q8 && !ES), "int8 LLRs: the decode and export builds");
     constexpr int SB = (DVH * QMAX + QMAX <= 127) ? 8 : 9;
     constexpr int EPL = (D + LPC - 1) / LPC;
     constexpr int VNW = DVH + 1;
@@ -203,6 +205,27 @@ k_bsc(std::conditional_t<ES, std::conditional_t<EW, BscArgsEw, BscArgsEs>, std::
             uint32_t Dq[8];
             gen_bytes(a.gen, blockIdx.x, v, a.qmax, Dq);
             pack_bytes<true>(Dq, valid, cs[u], cm[u], bg[u]);
+        } else if (L8 && v >= 0) {
+            // int8 LLRs (ldpc_decode_q8): a descriptor over the pack's valid rows, one byte per LLR
+            // (a row past the batch takes the last valid row's offset: masked by pack_bytes, and no
+            // load leaves the pack's rows); four rows per word, converted by
+            // l8_bytes (ldpc_bitplane.h); an invalid byte in a row of the pack marks the pack
+            const __amdgpu_buffer_rsrc_t l8_rs = __builtin_amdgcn_make_buffer_rsrc(
+                (void*)(reinterpret_cast<const uint8_t*>(a.llr) + b0 * nv), 0, nvalid * nv, 0x00020000);
+            uint32_t by[PACK], Dk[8];
+#pragma unroll
+            for (int r = 0; r < PACK; ++r)
+                by[r] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(l8_rs, v, min(r, nvalid - 1) * nv, 0);
+            uint32_t l8_bad = 0u;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                uint32_t iv;
+                Dk[i] = l8_bytes(by[4 * i] | by[4 * i + 1] << 8 | by[4 * i + 2] << 16 | by[4 * i + 3] << 24, a.qmax,
+                                 a.cu > 0.f, iv);
+                l8_bad |= l8_invalid(iv, valid >> (4 * i));
+            }
+            off |= l8_bad != 0u;
+            pack_bytes<true>(Dk, valid, cs[u], cm[u], bg[u]);
         } else if (v >= 0) {
             // (buffer loads: a wave-uniform descriptor over the pack's rows, the lane's 4 v in
             // voffset, the row's 4 r nv in soffset: no 64-bit VGPR address per load, as bsl)
@@ -225,6 +248,10 @@ k_bsc(std::conditional_t<ES, std::conditional_t<EW, BscArgsEw, BscArgsEs>, std::
                 if (a.flags) a.flags[b0 + tid] = 0x80;
                 if (a.n_iter) a.n_iter[b0 + tid] = 0;
             }
+        }
+        if constexpr (L8) {
+            // int8 LLRs: an invalid byte has no float decode to fall back to; marked the same way
+            if (tid < nvalid && a.flags) a.flags[b0 + tid] = 0x80;
         }
         if (tid == 0) a.bad[blockIdx.x] = 1u;
         return;
@@ -796,6 +823,9 @@ static bool bsc_b1_on() {
 }
 // the early-stop builds exist for these instances (on top of their B1 build)
 static constexpr bool bsc_es_inst(int i) { return i == 3 || i == 4; }
+// the instances with the int8-LLR builds: those the planner takes by default -- the
+// mixed-lane ones where every beta is 1, the first entry otherwise; not the A/B-only entries 1, 2
+static constexpr bool bsc_l8_inst(int i) { return i == 0 || i == 3 || i == 4; }
 
 // es: the plan of an early-stop request.  Only a decode that takes the B1 build
 // (every beta 1, one column table) on the instance the planner picks for it has such a build; the
@@ -1038,16 +1068,28 @@ struct BscLaunch : BscArgsEw {
     int word;                    // BscArgsXp::word
 };
 
-template <int I, bool XP, bool B1, bool Q8, bool ES = false, bool EW = false>
+template <int I, bool XP, bool B1, bool Q8, bool ES = false, bool EW = false, bool L8 = false>
 static int bsc_launch1(const BscLaunch& a, int nblocks, int nw, size_t lds, hipStream_t s) {
     constexpr BscInst k = kBscInst[I];
-    return bs_launch_kernel<&k_bsc<k.D, k.DVH, k.DVL, k.LPC, k.VPL, k.CPL, k.WPE, XP, 64 * k.NW, k.MIX, B1, Q8, ES, EW>>(
+    return bs_launch_kernel<&k_bsc<k.D, k.DVH, k.DVL, k.LPC, k.VPL, k.CPL, k.WPE, XP, 64 * k.NW, k.MIX, B1, Q8, ES, EW, L8>>(
         a, nblocks, nw, lds, s);
 }
 // instance I's launch: the build this decode takes
 template <int I>
-static int bsc_launch(const BscLaunch& a, int nblocks, int nw, size_t lds, hipStream_t s, bool q8, bool es) {
+static int bsc_launch(const BscLaunch& a, int nblocks, int nw, size_t lds, hipStream_t s, int src, bool es) {
     const bool b1 = bsc_b1_on() && a.beta_id && a.bcols == 1;
+    const bool q8 = src == BS_SRC_GEN;
+    if (src == BS_SRC_L8) {
+        // int8 LLRs: the decode and the word build (hdx with word) of the instances a plan takes
+        if constexpr (bsc_l8_inst(I)) {
+            if (es || a.hdw || (a.hdx && !a.word)) return LDPC_ERR_UNSUPPORTED;
+            if (a.hdx) return b1 ? bsc_launch1<I, true, true, false, false, false, true>(a, nblocks, nw, lds, s)
+                                 : bsc_launch1<I, true, false, false, false, false, true>(a, nblocks, nw, lds, s);
+            return b1 ? bsc_launch1<I, false, true, false, false, false, true>(a, nblocks, nw, lds, s)
+                      : bsc_launch1<I, false, false, false, false, false, true>(a, nblocks, nw, lds, s);
+        }
+        return LDPC_ERR_UNSUPPORTED;
+    }
     if (es) {
         // the early-stop builds (float LLRs, or the in-prologue channel): on the B1 build of the
         // instances that have them, one workgroup per pack, no export build; with a plane buffer
@@ -1074,7 +1116,7 @@ static int bsc_launch(const BscLaunch& a, int nblocks, int nw, size_t lds, hipSt
     return b1 ? bsc_launch1<I, false, true, false>(a, nblocks, nw, lds, s)
               : bsc_launch1<I, false, false, false>(a, nblocks, nw, lds, s);
 }
-typedef int (*BscLaunchFn)(const BscLaunch&, int, int, size_t, hipStream_t, bool, bool);
+typedef int (*BscLaunchFn)(const BscLaunch&, int, int, size_t, hipStream_t, int, bool);
 template <int... I>
 constexpr std::array<BscLaunchFn, sizeof...(I)> bsc_launch_table(std::integer_sequence<int, I...>) {
     return {&bsc_launch<I>...};
@@ -1161,6 +1203,11 @@ bool bsc_q8_ok(const DevGraph& g, const BsReq& r, bool has_short) {
     return p.ok && (!has_short || p.cu > 0.f) && q8_tab_fits(p);
 }
 
+bool bsc_l8_ok(const DevGraph& g, const BsReq& r, bool has_short) {
+    const BscPlan p = bsc_plan(g, r);
+    return p.ok && !r.es && bsc_l8_inst(p.inst) && (!has_short || p.cu > 0.f);
+}
+
 const char* bsc_kernel_name(const DevGraph& g, const BsReq& r) {
     static thread_local char buf[64];
     const BscPlan p = bsc_plan(g, r);
@@ -1190,7 +1237,8 @@ static int bsc_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const B
     a.off_u = p.off_u;
     a.hdw = o.hdw;
     a.word = o.word ? 1 : 0;
-    a.llr = llr;
+    // (int8 LLRs: the L8 builds read the bytes behind the same argument)
+    a.llr = r.l8 ? reinterpret_cast<const float*>(r.l8) : llr;
     a.gen = bs_gen(b, q8_tab_lds(p));    // the in-prologue channel (ldpc_decode_awgn)
     a.B = b.B;
     a.n_vars = g.n_vars;
@@ -1230,7 +1278,7 @@ static int bsc_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const B
     a.off_blut = p.off_blut;
     const int nblocks = (int)((b.B + PACK - 1) / PACK);
     static constexpr auto kLaunch = bsc_launch_table(std::make_integer_sequence<int, kBscNInst>{});
-    return kLaunch[p.inst](a, nblocks, p.nw, p.lds, s, b.q8 != nullptr, r.es);
+    return kLaunch[p.inst](a, nblocks, p.nw, p.lds, s, r.l8 ? BS_SRC_L8 : b.q8 ? BS_SRC_GEN : BS_SRC_LLR, r.es);
 }
 
 // (bs_decode falls through to it; LDPC_ERR_UNSUPPORTED with nothing launched when no build serves

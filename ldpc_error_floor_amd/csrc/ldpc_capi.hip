@@ -864,6 +864,67 @@ int ldpc_decode_word(ldpc_ctx* c, const float* llr_dev, int64_t B, const ldpc_de
     return decode_bs_impl(c, llr_dev, B, p, false, bs_outs(o), stream, nullptr, nullptr);
 }
 
+// ---- int8 quantized LLRs: the counters-only decode and the word mode on the
+// bit-sliced kernels' L8 builds, no v5 fixup (an invalid pack is marked by the kernel) -----------
+// the request when the L8 builds decode it (has_short: the input may hold the +-clip markers)
+static int q8_request(const ldpc_ctx* c, int64_t B, const ldpc_decode_params* p, bool has_short, BsReq* r) {
+    const int rq = bs_request(c, B, p, false, r);
+    if (rq != LDPC_OK) return rq;
+    return bs_l8_ok(c->g->dev, *r, has_short) ? LDPC_OK : LDPC_ERR_UNSUPPORTED;
+}
+
+int ldpc_q8_supported(const ldpc_ctx* c, const ldpc_decode_params* p, int32_t has_short, int32_t word) {
+    if (!c || !p) return LDPC_ERR_ARG;
+    (void)word;                    // (both kinds are served on the same plans)
+    BsReq r{};
+    const int st = q8_request(c, 1, p, has_short != 0, &r);
+    return st == LDPC_OK ? 1 : st == LDPC_ERR_UNSUPPORTED ? 0 : st;
+}
+
+static int decode_q8_impl(ldpc_ctx* c, const int8_t* q8_dev, int64_t B, const ldpc_decode_params* p, const BsOuts& o,
+                          uint32_t* iter_wrong, void* stream) {
+    BsReq r{};
+    // (markers in the input are invalid bytes where the plan has no shortened-bit path: the kernel
+    // marks their packs, so the request itself is served either way)
+    const int rq = q8_request(c, B, p, false, &r);
+    if (rq != LDPC_OK) return rq;
+    r.l8 = q8_dev;
+    ldpc_graph* g = c->g;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    DeviceGuard dg(g->device);
+    Bufs b = make_bufs(c, B, p);
+    b.iter_wrong = iter_wrong;
+    if (iter_wrong && hipMemsetAsync(iter_wrong, 0, (size_t)p->T * ((B + 31) / 32) * sizeof(uint32_t), s) != hipSuccess)
+        return LDPC_ERR_HIP;
+    BsOut bo{};
+    bo.counters = o.counters;
+    bo.flags = o.frame_flags;
+    const int st = fused_decode_bs(g->dev, b, c->fused, nullptr, r, c->B_max, c->ntiles_max, bo, o.rows, o.word_flags, s);
+    if (st != LDPC_OK) return st;
+    set_last_kernel(c, bs_kernel_name(g->dev, r), o.rows ? ",word" : nullptr, false);
+    std::strncat(c->last_kernel, "+q8", sizeof(c->last_kernel) - std::strlen(c->last_kernel) - 1);
+    return hipGetLastError() == hipSuccess ? LDPC_OK : LDPC_ERR_HIP;
+}
+
+int ldpc_decode_q8(ldpc_ctx* c, const int8_t* q8_dev, int64_t B, const ldpc_decode_params* p,
+                   const ldpc_decode_outputs* o, void* stream) {
+    // (the input, the outputs' size and the exports this mode has none of: before the context is read)
+    if (!q8_dev || !p) return LDPC_ERR_ARG;
+    if (p->outputs_size != 0 && p->outputs_size != (int32_t)sizeof(ldpc_decode_outputs)) return LDPC_ERR_ARG;
+    if (o && (o->app_all || o->hard_bits || o->synd_bits)) return LDPC_ERR_ARG;
+    if (!c) return LDPC_ERR_ARG;
+    const bool full = o && p->outputs_size == (int32_t)sizeof(ldpc_decode_outputs);
+    const BsOuts bo{o ? o->counters : nullptr, o ? o->frame_flags : nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    return decode_q8_impl(c, q8_dev, B, p, bo, full ? o->iter_wrong : nullptr, stream);
+}
+
+int ldpc_decode_q8_word(ldpc_ctx* c, const int8_t* q8_dev, int64_t B, const ldpc_decode_params* p,
+                        const ldpc_word_outputs* o, void* stream) {
+    if (!q8_dev || !o || o->size != (int32_t)sizeof(ldpc_word_outputs) || !o->hard_last) return LDPC_ERR_ARG;
+    if (!c || !p) return LDPC_ERR_ARG;
+    return decode_q8_impl(c, q8_dev, B, p, bs_outs(o), nullptr, stream);
+}
+
 // ---- the events mode: the word modes' decode, events_out in word_out's place ----
 static_assert(sizeof(ldpc_event_outputs) == 96, "ldpc_event_outputs is part of ABI 3");
 // (the outputs' size, the required pointers and cap, checked before the context is read)

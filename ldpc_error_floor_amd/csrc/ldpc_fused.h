@@ -19,9 +19,9 @@ struct FusedWorkspace {
     size_t bs_lut_bytes = 0;
     uint32_t* bs_bad = nullptr;    // [packs] 1: pack decoded by the v5 fixup
     int64_t bs_bad_n = 0;
-    int bs_resident[5] = {0, 0, 0, 0, 0};   // bit-sliced kernel with the pack loop: the workgroups resident
+    int bs_resident[7] = {0, 0, 0, 0, 0, 0, 0};   // bit-sliced kernel with the pack loop: the workgroups resident
     uint64_t bs_resident_key = ~0ull; // at once (decode / export / channel build, the frozen decode /
-                                      // channel build), and what for
+                                      // channel build, the int8 decode / word build), and what for
     uint32_t* bs_ticket = nullptr; // the pack loop's ticket word (ldpc_bs_kernel.h, BS_RED_NEXT): allocated
                                    // at the first launch that wants it, zeroed before each one
     bool bs_frozen = false;        // the last bit-sliced decode ran a geometry-frozen build
@@ -94,6 +94,8 @@ struct BsReq {
     float clip;
     int T;
     bool es;
+    const int8_t* l8 = nullptr;    // the LLRs as int8 grid values [B][n_vars] (device; ldpc_decode_q8,
+                                   // DESIGN 3.11) instead of the float LLRs, or null; no part of the plan
 };
 // What one decode writes; null: off.
 struct BsOut {
@@ -116,12 +118,17 @@ struct BsOut {
 // kernel_name: "bsl[...]" / "bsc[...]", with ",es" inside the brackets for early stop; "" if unserved.
 bool bs_supported(const DevGraph& g, const BsReq& r);
 bool bs_q8_ok(const DevGraph& g, const BsReq& r, bool has_short);
+// l8_ok: the int8-LLR builds (BsReq::l8) serve the request: its plan's instance has
+// them and, with has_short (the +-clip markers in the input), decodes shortened bits
+bool bs_l8_ok(const DevGraph& g, const BsReq& r, bool has_short);
+bool bsc_l8_ok(const DevGraph& g, const BsReq& r, bool has_short);
 const char* bs_kernel_name(const DevGraph& g, const BsReq& r);
 bool bsc_supported(const DevGraph& g, const BsReq& r);
 bool bsc_q8_ok(const DevGraph& g, const BsReq& r, bool has_short);
 const char* bsc_kernel_name(const DevGraph& g, const BsReq& r);
-// the decode of b.B codewords (LLRs at llr, or the in-prologue channel b.q8 / b.gen8).  Packs with
-// an LLR off the grid are marked in o.bad (early stop: also flags 0x80, n_iter 0), not decoded.
+// the decode of b.B codewords (LLRs at llr, the in-prologue channel b.q8 / b.gen8, or int8 LLRs at
+// r.l8).  Packs with an LLR off the grid are marked in o.bad (early stop and int8 LLRs: also flags
+// 0x80; early stop: n_iter 0), not decoded.
 // LDPC_ERR_UNSUPPORTED: no build serves the request; nothing was launched.
 int bs_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float* llr, const BsReq& r,
               const BsOut& o, hipStream_t s);

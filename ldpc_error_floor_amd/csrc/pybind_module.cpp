@@ -340,6 +340,83 @@ PYBIND11_MODULE(_ldpc_nms, m) {
         },
         py::arg("ctx"), py::arg("T"), py::arg("decoding_type"), py::arg("q_bit"),
         py::arg("target_bits"), py::arg("kernel"), py::arg("clip_llr") = 20.0f);
+    // int8 quantized LLRs (ldpc_decode_q8 / ldpc_decode_q8_word / ldpc_q8_supported)
+    m.def(
+        "decode_q8",
+        [](Ctx& c, uintptr_t q8, int64_t B, int T, int decoding_type, int q_bit, int target_bits,
+           float clip, int kernel, uintptr_t counters, uintptr_t flags, uintptr_t iter_wrong, uintptr_t stream) {
+            ldpc_decode_params p = make_params(T, decoding_type, q_bit, target_bits, clip, kernel);
+            ldpc_decode_outputs o{};
+            o.counters = reinterpret_cast<int64_t*>(counters);
+            o.frame_flags = reinterpret_cast<uint8_t*>(flags);
+            o.iter_wrong = reinterpret_cast<uint32_t*>(iter_wrong);
+            int st;
+            {
+                py::gil_scoped_release nogil;
+                st = ldpc_decode_q8(c.h, reinterpret_cast<const int8_t*>(q8), B, &p, &o,
+                                    reinterpret_cast<void*>(stream));
+            }
+            check(st, "ldpc_decode_q8");
+        },
+        py::arg("ctx"), py::arg("q8"), py::arg("B"), py::arg("T"), py::arg("decoding_type"),
+        py::arg("q_bit"), py::arg("target_bits"), py::arg("clip"), py::arg("kernel"),
+        py::arg("counters") = 0, py::arg("flags") = 0, py::arg("iter_wrong") = 0, py::arg("stream") = 0);
+    m.def(
+        "decode_q8_word",
+        [](Ctx& c, uintptr_t q8, int64_t B, int T, int decoding_type, int q_bit, int target_bits,
+           float clip, int kernel, uintptr_t hard_last, uintptr_t word_flags, uintptr_t counters,
+           uintptr_t flags, uintptr_t stream) {
+            ldpc_decode_params p = make_params(T, decoding_type, q_bit, target_bits, clip, kernel);
+            ldpc_word_outputs o{};
+            o.size = (int32_t)sizeof(ldpc_word_outputs);
+            o.hard_last = reinterpret_cast<uint32_t*>(hard_last);
+            o.word_flags = reinterpret_cast<uint8_t*>(word_flags);
+            o.counters = reinterpret_cast<int64_t*>(counters);
+            o.frame_flags = reinterpret_cast<uint8_t*>(flags);
+            int st;
+            {
+                py::gil_scoped_release nogil;
+                st = ldpc_decode_q8_word(c.h, reinterpret_cast<const int8_t*>(q8), B, &p, &o,
+                                         reinterpret_cast<void*>(stream));
+            }
+            check(st, "ldpc_decode_q8_word");
+        },
+        py::arg("ctx"), py::arg("q8"), py::arg("B"), py::arg("T"), py::arg("decoding_type"),
+        py::arg("q_bit"), py::arg("target_bits"), py::arg("clip"), py::arg("kernel"),
+        py::arg("hard_last"), py::arg("word_flags") = 0, py::arg("counters") = 0, py::arg("flags") = 0,
+        py::arg("stream") = 0);
+    m.def(
+        "q8_supported",
+        [](Ctx& c, int T, int decoding_type, int q_bit, int target_bits, int kernel, float clip, bool has_short,
+           bool word) {
+            ldpc_decode_params p = make_params(T, decoding_type, q_bit, target_bits, clip, kernel);
+            const int st = ldpc_q8_supported(c.h, &p, has_short ? 1 : 0, word ? 1 : 0);
+            check(st, "ldpc_q8_supported");
+            return st == 1;
+        },
+        py::arg("ctx"), py::arg("T"), py::arg("decoding_type"), py::arg("q_bit"),
+        py::arg("target_bits"), py::arg("kernel"), py::arg("clip_llr") = 20.0f, py::arg("has_short") = false,
+        py::arg("word") = false);
+    m.def(
+        "channel_awgn_q8",
+        [](uintptr_t q8, int64_t B, int n_vars, double sigma, uint64_t seed, int64_t offset, int q_bit, int ps,
+           int pe, int ss, int se, uintptr_t stream) {
+            check(ldpc_channel_awgn_q8(reinterpret_cast<int8_t*>(q8), B, n_vars, sigma, seed, offset, q_bit, ps,
+                                       pe, ss, se, reinterpret_cast<void*>(stream)),
+                  "ldpc_channel_awgn_q8");
+        },
+        py::arg("q8"), py::arg("B"), py::arg("n_vars"), py::arg("sigma"), py::arg("seed"), py::arg("offset"),
+        py::arg("q_bit"), py::arg("punct_start"), py::arg("punct_end"), py::arg("short_start"),
+        py::arg("short_end"), py::arg("stream") = 0);
+    m.def(
+        "llr_to_q8",
+        [](uintptr_t llr, int64_t n, int q_bit, float clip, uintptr_t q8, uintptr_t n_invalid, uintptr_t stream) {
+            check(ldpc_llr_to_q8(reinterpret_cast<const float*>(llr), n, q_bit, clip, reinterpret_cast<int8_t*>(q8),
+                                 reinterpret_cast<int64_t*>(n_invalid), reinterpret_cast<void*>(stream)),
+                  "ldpc_llr_to_q8");
+        },
+        py::arg("llr"), py::arg("n"), py::arg("q_bit"), py::arg("clip"), py::arg("q8"), py::arg("n_invalid") = 0,
+        py::arg("stream") = 0);
     // floor events (ldpc_decode_events / ldpc_decode_awgn_events / ldpc_events_supported)
     m.def(
         "decode_events",

@@ -22,6 +22,8 @@ from .weights import DecoderWeights
 __all__ = ["NMSDecoder", "Decoder", "DecodeResult", "KERNELS"]
 
 KERNELS = {"auto": 0, "flood": 1, "fused": 2}
+# the q8 format's grids: q_bit -> (step, qmax); a byte is LLR / step
+Q8_GRIDS = {5: (0.5, 15), -5: (1.0, 15), 4: (1.0, 7), 3: (2.0, 3)}
 
 
 @dataclass
@@ -496,6 +498,200 @@ class NMSDecoder:
                          ptr(res.app), ptr(res.hard), ptr(res.synd), ptr(res.counters),
                          ptr(res.flags), stream.cuda_stream, ptr(res.iter_wrong))
         return res
+
+    # ---- int8 quantized LLRs ----------------------------------------------------
+    def _q8_grid(self):
+        """(step, qmax) of the bytes this decoder takes: its quantizer grid (``Q8_GRIDS``).  The
+        float modes and q = 6 have no such grid and no int8 kernel; for them, which only
+        ``decode_q8``'s dequantizing fallback serves, a byte is the LLR itself (step 1, |g| <= 126)."""
+        if self.decoding_type == DECODING_QMS and self.q_bit in Q8_GRIDS:
+            return Q8_GRIDS[self.q_bit]
+        return (1.0, 126)
+
+    def supports_q8(self, has_short: bool = False, word: bool = False, T=None, kernel=None) -> bool:
+        """Whether ``decode_q8`` runs the bit-sliced kernels' int8 builds for this decoder
+        (``ldpc_q8_supported``) -- exactly where they serve the float decode of the same kind
+        (counters / flags / iter_wrong, or with ``word`` the ``hard_last`` mode) -- and, with
+        ``has_short``, decodes the +-clip markers of shortened bits.  Where it is false (q = 6, the
+        float modes, flood, per-edge weights, other graphs) ``decode_q8`` dequantizes and calls
+        ``decode``."""
+        T = self.T if T is None else int(T)
+        if T > self.T or self.decoding_type != DECODING_QMS or self.q_bit not in Q8_GRIDS:
+            return False
+        ctx = self._ensure_ctx(1, T)
+        return bool(self._ext.q8_supported(ctx, T, self.decoding_type, self.q_bit, self.target_bits,
+                                           KERNELS[kernel or self.kernel], self.clip, bool(has_short), bool(word)))
+
+    def quantize_q8(self, llr, strict: bool = True):
+        """Float LLRs -> the q8 bytes (int8, same shape): ``rint(llr / step)`` where the value is on
+        the grid and within +-qmax, -128 / +127 for -clip / +clip.  Any other value has no byte:
+        ``strict=True`` raises ``ValueError``, ``strict=False`` stores it saturated to +-qmax.  A
+        tensor on the decoder's device is converted there (``ldpc_llr_to_q8``), anything else on
+        the host."""
+        torch = self._torch
+        step, qmax = self._q8_grid()
+        native = self.decoding_type == DECODING_QMS and self.q_bit in Q8_GRIDS
+        if native and isinstance(llr, torch.Tensor) and llr.device.type == "cuda":
+            x = llr.to(dtype=torch.float32).contiguous()
+            out = torch.empty(x.shape, dtype=torch.int8, device=x.device)
+            bad = torch.zeros(1, dtype=torch.int64, device=x.device)
+            if x.numel():
+                with torch.cuda.device(x.device):
+                    self._ext.llr_to_q8(x.data_ptr(), x.numel(), self.q_bit, self.clip, out.data_ptr(), bad.data_ptr(),
+                                        torch.cuda.current_stream(x.device).cuda_stream)
+            nbad = int(bad.item()) if strict else 0
+        else:
+            x = np.asarray(llr.cpu().numpy() if isinstance(llr, torch.Tensor) else llr, dtype=np.float32)
+            g = x * np.float32(1.0 / step)
+            q = np.clip(np.rint(np.nan_to_num(g, nan=0.0)), -qmax, qmax)
+            lo, hi = x == np.float32(-self.clip), x == np.float32(self.clip)
+            ok = q == g
+            q = np.where(~ok & lo, -128, np.where(~ok & hi, 127, q)).astype(np.int8)
+            nbad = int((~(ok | lo | hi)).sum())
+            out = torch.from_numpy(q)
+        if strict and nbad:
+            raise ValueError(f"quantize_q8: {nbad} values are neither on the q_bit={self.q_bit} grid "
+                             f"(multiples of {step} within +-{qmax * step}) nor +-clip_LLR")
+        return out
+
+    def dequantize_q8(self, q8):
+        """The float LLRs q8 bytes stand for (float32, same shape, on the input's device):
+        ``g * step``, -128 / +127 -> -clip / +clip.  (An invalid byte maps to ``g * step``, off the
+        range of the grid.)"""
+        torch = self._torch
+        step, _ = self._q8_grid()
+        q = q8 if isinstance(q8, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(q8, np.int8)))
+        if q.dtype != torch.int8:
+            raise ValueError("q8 must be int8")
+        x = q.to(torch.float32) * step
+        x = torch.where(q == -128, torch.full_like(x, -self.clip), x)
+        return torch.where(q == 127, torch.full_like(x, self.clip), x)
+
+    def _as_q8(self, q8):
+        torch = self._torch
+        if not isinstance(q8, torch.Tensor):
+            a = np.asarray(q8)
+            if a.dtype != np.int8:
+                raise ValueError("q8 must be int8")
+            q8 = torch.from_numpy(np.ascontiguousarray(a))
+        if q8.dtype != torch.int8:
+            raise ValueError("q8 must be int8 (decode() takes LLRs of any other dtype)")
+        q8 = q8.to(device=self.device)
+        B = q8.shape[0]
+        q8 = q8.reshape(B, -1) if B else q8.reshape(0, self.n_vars)
+        if q8.shape[1] != self.n_vars:
+            raise ValueError(f"q8 has {q8.shape[1]} bits per codeword, graph has {self.n_vars}")
+        # (rows of n_vars bytes back to back; any start address: the kernels load single bytes)
+        return q8 if q8.is_contiguous() else q8.contiguous()
+
+    def _q8_invalid_rows(self, q8):
+        """bool [B]: the rows of a q8 tensor that hold an invalid byte (markers taken as valid)."""
+        _, qmax = self._q8_grid()
+        ok = ((q8 >= -qmax) & (q8 <= qmax)) | (q8 == -128) | (q8 == 127)
+        return ~ok.all(dim=1)
+
+    def decode_q8(self, q8, T: Optional[int] = None, counters=None, flags=False, iter_wrong: bool = False,
+                  hard_last=False, word_flags: bool = False, kernel: Optional[str] = None, stream=None,
+                  on_invalid: str = "raise", app: bool = False, hard: bool = False, synd: bool = False,
+                  target_bits: Optional[int] = None) -> DecodeResult:
+        """Decode int8 quantized LLRs: ``q8`` is int8 ``[B, N*z]``, the LLR in grid
+        units ``g = LLR / step`` with ``-qmax <= g <= qmax``, -128 / +127 for a shortened bit's
+        -clip / +clip (``quantize_q8`` makes it, ``awgn_q8`` generates it).  Every output equals,
+        bit for bit, ``decode`` of ``dequantize_q8(q8)``: ``counters``, ``flags``, ``iter_wrong``,
+        and with ``hard_last`` (``True`` or a caller-owned tensor) the decoded words and
+        ``word_flags``.  The bit-sliced kernels read the bytes directly (a quarter of the float
+        input), with no fixup launch.
+
+        Any other byte is invalid, and so is a marker where ``supports_q8(has_short=True)`` is
+        false.  A pack of 32 frames holding one is not decoded: ``flags`` (and ``word_flags``) 0x80,
+        zero rows, nothing in the counters or ``iter_wrong``.  ``on_invalid="raise"`` synchronises
+        and raises ``ValueError`` naming the first such frame; ``"mark"`` returns the result as it
+        is.
+
+        Where ``supports_q8`` is false, or ``app`` / ``hard`` / ``synd`` is asked for, the bytes are
+        dequantized and ``decode`` runs (``last_kernel()`` tells); invalid bytes are then checked
+        on the device for ``"raise"`` and decoded as ``decode`` decodes off-grid LLRs for
+        ``"mark"``."""
+        torch = self._torch
+        if on_invalid not in ("raise", "mark"):
+            raise ValueError("on_invalid must be 'raise' or 'mark'")
+        T = self.T if T is None else int(T)
+        nt = self.target_bits if target_bits is None else int(target_bits)
+        if T > self.T:
+            raise ValueError(f"T={T} exceeds the {self.T} iterations the weights cover")
+        word = hard_last is not False and hard_last is not None
+        if word_flags and not word:
+            raise ValueError("word_flags is an output of hard_last=True")
+        if word and iter_wrong:
+            raise ValueError("hard_last serves word_flags, counters and flags only, not iter_wrong")
+        q8 = self._as_q8(q8)
+        B = int(q8.shape[0])
+        if app or hard or synd or not self.supports_q8(word=word, T=T, kernel=kernel):
+            if on_invalid == "raise" and B:
+                badrows = self._q8_invalid_rows(q8)
+                if bool(badrows.any().item()):
+                    first = int(badrows.nonzero()[0].item())
+                    raise ValueError(f"decode_q8: frame {first} holds a byte that is no q8 value "
+                                     "(on_invalid='mark' decodes it as an off-grid LLR)")
+            return self.decode(self.dequantize_q8(q8), T=T, app=bool(app), hard=hard, synd=synd, counters=counters,
+                               flags=flags, kernel=kernel, stream=stream, target_bits=target_bits,
+                               iter_wrong=iter_wrong, hard_last=hard_last, word_flags=word_flags,
+                               on_off_grid="mark")
+        dev = self.device
+        res = self._word_result(B, hard_last) if word else DecodeResult()
+        asked = flags is not None and flags is not False
+        check = on_invalid == "raise"
+        self._es_outputs(res, B, T, counters, flags if asked else check, False, None)
+        if word and word_flags:
+            res.word_flags = torch.empty(B, dtype=torch.uint8, device=dev)
+        if iter_wrong:
+            res.iter_wrong = torch.empty((T, (B + 31) // 32), dtype=torch.int32, device=dev)
+        if B == 0:
+            return res
+        ctx = self._ensure_ctx(B, T)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        ptr = lambda t: 0 if t is None else t.data_ptr()   # noqa: E731
+        if word:
+            self._ext.decode_q8_word(ctx, q8.data_ptr(), B, T, self.decoding_type, self.q_bit, nt, self.clip,
+                                     KERNELS[kernel or self.kernel], res.hard_last.data_ptr(), ptr(res.word_flags),
+                                     ptr(res.counters), ptr(res.flags), stream.cuda_stream)
+        else:
+            self._ext.decode_q8(ctx, q8.data_ptr(), B, T, self.decoding_type, self.q_bit, nt, self.clip,
+                                KERNELS[kernel or self.kernel], ptr(res.counters), ptr(res.flags),
+                                ptr(res.iter_wrong), stream.cuda_stream)
+        if check:
+            stream.synchronize()
+            marked = (res.flags[:B] == 0x80).nonzero()
+            if marked.numel():
+                raise ValueError(f"decode_q8: frame {int(marked[0].item())} is the first of {int(marked.numel())} "
+                                 "frames in packs holding a byte that is no q8 value; they were not decoded "
+                                 "(on_invalid='mark' returns them marked)")
+            if not asked:
+                res.flags = None
+        return res
+
+    def awgn_q8(self, B: int, sigma: float, seed: int, offset: int = 0, punct=None, short=None,
+                out=None, stream=None):
+        """``awgn`` as q8 bytes (int8 [B, N*z]; ``ldpc_channel_awgn_q8``): the same Philox stream
+        and level sampler, so it equals ``quantize_q8(awgn(...))``; punctured bits 0, shortened
+        bits -128."""
+        torch = self._torch
+        if self.decoding_type != DECODING_QMS or self.q_bit not in Q8_GRIDS:
+            raise ValueError("awgn_q8 covers the QMS grids q_bit 5, -5, 4 and 3 only")
+        punct = getattr(self, "punct", (0, 0)) if punct is None else punct
+        short = getattr(self, "short", (0, 0)) if short is None else short
+        if out is None:
+            out = torch.empty((B, self.n_vars), dtype=torch.int8, device=self.device)
+        elif (out.dtype != torch.int8 or out.device != self.device or not out.is_contiguous() or
+              out.numel() < B * self.n_vars):
+            raise ValueError("out must be a contiguous int8 [B, N*z] tensor on the decoder's device")
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        self._ext.channel_awgn_q8(out.data_ptr(), int(B), self.n_vars, float(sigma), int(seed), int(offset),
+                                  self.q_bit, int(punct[0]), int(punct[1]), int(short[0]), int(short[1]),
+                                  stream.cuda_stream)
+        return out
 
     def generates_channel_in_kernel(self, T=None, kernel=None, app: bool = False) -> bool:
         """Whether a counters-only ``decode_awgn`` (``app``: one with an APP export) generates
