@@ -133,6 +133,13 @@ int ldpc_ctx_last_kernel(const ldpc_ctx* c, char* name, int32_t name_len);
    variable LDPC_BS_FROZEN=0, read at every launch, forces the generic build. */
 int ldpc_ctx_last_frozen(const ldpc_ctx* c);
 
+/* 1 when the last successful decode on this context ran a bit-sliced kernel ("bsl[...]") that
+   weighed its check minima through the fixed-set immediate tables (one alpha per iteration, q = 5
+   or -5, every iteration's table in the set; same name, same results), 0 when it read the tables
+   from LDS or another kernel ran; LDPC_ERR_ARG for a null context.  The environment variable
+   LDPC_BS_AFIX=0, read at every launch, forces the LDS tables. */
+int ldpc_ctx_last_afix(const ldpc_ctx* c);
+
 /* On-GPU AWGN channel for the all-zero codeword (create_mix_epoch, Print_Functions.py:29-72):
    writes llr_dev [B][n_vars] f32 = Q(2(sigma*n - 1)/sigma^2) with punctured (1-based bits
    punct_start..punct_end, 0 = none) -> 0 and shortened -> -clip_llr.  Counter-based Philox

@@ -55,6 +55,20 @@ int ldpc_debug_bs_frozen(const int32_t* proto, int32_t M, int32_t N, int32_t z, 
                          float clip, int32_t* plan, int32_t* frozen, int32_t n, char* names,
                          int32_t names_len);
 
+/* The place in the fixed table set (csrc/ldpc_beta_tabs.h, kBetaTab) of the check table the
+ * bit-sliced kernels build for one weight alpha: mode 1 (q = 5) or 2 (q = -5), the modes of
+ * csrc/ldpc_host.h; host only.  *out_id = the index, or -1 when the table is not in the set or the
+ * mode is another; table (16 bytes, or NULL) takes the set's row of that index (untouched at -1).
+ * Returns a status of ldpc_nms.h. */
+int ldpc_debug_alpha_tid(float alpha, int32_t mode, int32_t* out_id, uint8_t* table);
+
+/* The check-table ids a weight set [T][E] (alpha_ucn [T][E] or NULL) gets on a proto graph
+ * (host::analyze_weights, what ldpc_weights_set uploads): ids [T] takes them.  Returns 1 when the
+ * ids are filled (alpha one value per iteration and no UCN weights), 0 when there are none (ids
+ * untouched: the kernels' argument stays null), or a negative status.  Host only. */
+int ldpc_debug_alpha_tids(const int32_t* proto, int32_t M, int32_t N, int32_t z, int32_t T,
+                          const float* alpha, const float* alpha_ucn, int32_t* ids);
+
 /* The event collector of ldpc_decode_events (csrc/ldpc_events.hip, events_out) on caller-supplied
  * device buffers instead of a decode's: planes_dev [ceil(B/32)][N*z], bit r of word (pack, v) =
  * variable v of frame 32 pack + r (the bits of a ragged last pack's frames past B may hold

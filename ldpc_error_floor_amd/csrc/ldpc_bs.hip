@@ -878,6 +878,16 @@ static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const Bs
     // the fixed-set channel tables cover the grids whose magnitudes saturate at 15 (q = 5, -5)
     a.btid = (bs_qmax(r.mode) == QMAX && !getenv("LDPC_BS_NOBFIX")) ? g.beta_tid : nullptr;
     a.btid_n = g.N;
+    // the check tables' ids: the pack-loop instances, one alpha per iteration, the same grids, and
+    // every table of the weight set in the fixed set (w_alpha_tid_dev is null otherwise: one decision
+    // per weight set, ldpc_weights_set); LDPC_BS_AFIX=0, read at every launch like
+    // LDPC_BS_TICKETS, keeps the tables in LDS
+    a.atid = nullptr;
+    if (bs_loops(k) && !p.ucn && p.arows == 1 && (r.mode == MODE_Q5 || r.mode == MODE_QM5)) {
+        const char* e = getenv("LDPC_BS_AFIX");
+        if (e ? atoi(e) != 0 : true) a.atid = g.host->w_alpha_tid_dev;
+    }
+    ws.bs_afix = a.atid != nullptr;
     a.counters = o.counters;
     a.flags = o.flags;
     a.bad = o.bad;
@@ -989,6 +999,7 @@ int bs_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float*
     bool to_bsc;
     BsPlan p = bs_route(g, r, &to_bsc);
     ws.bs_frozen = false;
+    ws.bs_afix = false;
     if (!p.ok) return to_bsc ? bsc_decode(g, b, ws, llr, r, o, s) : LDPC_ERR_UNSUPPORTED;
     const bool frozen = bs_frozen_fit(g, p, r, o.hdx != nullptr || o.hdw != nullptr);
     return bs_run(g, b, ws, p, llr, r, o, frozen, s);

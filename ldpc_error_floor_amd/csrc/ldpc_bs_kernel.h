@@ -619,6 +619,17 @@ constexpr bool bs_loops(const BsInst& k) { return k.VPL == 1 && k.CPL == 1 && !k
 #else
 #define BS_LOOP_TU 0
 #endif
+// The arguments of the pack-loop units' builds (kBsInst 0-2, every build of theirs): the build's
+// own struct and, appended, the check tables' places in the fixed set, so that no existing field
+// moves and the other instances' kernel arguments stay as they are.
+template <class K>
+struct BsArgsAf : K {
+    const int32_t* atid;         // [T] kBetaTab index of iteration t's check table Q(relu(alpha m))
+                                 // (host::WeightInfo::alpha_tid, every entry >= 0), or null: the
+                                 // check phase reads the alpha tables from LDS
+};
+template <class K>
+using BsKernArgs = std::conditional_t<BS_LOOP_TU != 0, BsArgsAf<K>, K>;
 // How the pack loop hands out its packs.  A workgroup's first pack is blockIdx.x; every pack's
 // prologue takes the ticket of the pack after it -- one lane's returning atomic add on the launch's
 // ticket word, issued ahead of the channel's loads (the in-prologue channel: ahead of the sampler's
@@ -671,7 +682,7 @@ constexpr int BS_RED_NEXT = 8;
 template <int D, int DV, int LPC, int VPL, int CPL, bool UCN, bool BIG, bool PK, int WPE, bool XP, int LB, bool Q8,
           bool ES = false, bool EW = false, bool FZ = false, bool L8 = false>
 __global__ void __launch_bounds__(LB) __attribute__((amdgpu_waves_per_eu(WPE)))
-k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::conditional_t<XP, BsArgsXp, BsArgs>> a) {
+k_bs(BsKernArgs<std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::conditional_t<XP, BsArgsXp, BsArgs>>> a) {
     static_assert(LPC == 2 || LPC == 4, "lanes per check");
     using KArgs = std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::conditional_t<XP, BsArgsXp, BsArgs>>;
     static_assert(!ES || (UCN && VPL == 1 && CPL == 1 && !XP), "early stop: one-chunk UCN-compiled instances");
@@ -718,6 +729,10 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
     // the channel-table ids of the next variable phase loaded before the check phase: the
     // multi-chunk instances (one workgroup per CU: nothing else hides the L2 round trip)
     constexpr bool BKPF = !XP && VPL > 1;
+    // AFX: the build can weigh the check minima through the fixed-set tables (beta_asm) when the
+    // launch gives their ids (BsArgsAf::atid): the pack-loop units
+    constexpr bool AFX = BS_LOOP_TU != 0;
+    static_assert(!AFX || (ONE && !UCN), "fixed-set check tables: the one-chunk instances without UCN");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if ((uint32_t)(uintptr_t)smem != 0u) __builtin_trap();          // slots are LDS-absolute
 #ifdef BS_STAMP
@@ -1415,6 +1430,21 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
             RED[1] &= w0;
         }
         const int nx = (t + 1) & 1;
+        // the fixed-set id of this iteration's check table (AFX builds, ids given): one scalar
+        // load through the constant address space, used after the minima search.  The ids'
+        // address comes from the kernel arguments again each iteration, behind an opaque pointer:
+        // it is not held through the loop, and the loop is not duplicated over the
+        // launch-uniform choice.
+        int ak = 0;
+        bool afx = false;
+        if constexpr (AFX) {
+            typedef __attribute__((address_space(4))) const BsArgsAf<KArgs> ConstAf;
+            ConstAf* kq = (ConstAf*)__builtin_amdgcn_kernarg_segment_ptr();
+            asm volatile("" : "+s"(kq));
+            const ConstW* at = (const ConstW*)kq->atid;
+            afx = at != nullptr;
+            if (afx) ak = (int)at[t];
+        }
 #pragma unroll
         for (int u = 0; u < VPL; ++u) asm volatile("" : "+s"(dw[u]), "+s"(dwmin[u]));   // compared per use, not hoisted as masks
         if (!RPW) asm volatile("" : "+s"(cn_dmin));
@@ -1455,7 +1485,9 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
                     off_bl = ka->off_blut;
                 }
             }
-            copy_async(off_al + 4u * (uint32_t)(nx * al), alut_p + (size_t)(t + 1) * al, al, cw, NT);
+            // (no alpha table where the check phase takes the fixed set's: its LDS region stays unused)
+            if (!(AFX && afx))
+                copy_async(off_al + 4u * (uint32_t)(nx * al), alut_p + (size_t)(t + 1) * al, al, cw, NT);
             if (bcl > 1)
                 copy_async(off_bl + 4u * (uint32_t)(nx * bl), blut_p + (size_t)(t + 1) * bl, bl, cw, NT);
         }
@@ -1602,7 +1634,13 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
             // weighted, quantized minima: each lane evaluates OB output bits, the group shares them
             uint32_t q1[4], q2[4];
             PH9("ck_tab", c, m1, m2, par);
-            {
+            if (AFX && afx) {
+                // alpha_t's table is table ak of the fixed set: both minima of the group, which
+                // every lane of it holds, through the immediate truth tables -- all four planes in
+                // each lane, no table words from LDS and no exchange over the lane group
+                beta_asm(q1, m1, ak);
+                beta_asm(q2, m2, ak);
+            } else {
                 const uint32_t mm[2][4] = {{m1[0], m1[1], m1[2], m1[3]}, {m2[0], m2[1], m2[2], m2[3]}};
                 const uint32_t tab = ctab + (uint32_t)((t & 1) * AL * 4);
                 uint32_t qb[OB][2];
@@ -1881,6 +1919,7 @@ k_bs(std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::con
 // the argument struct that kernel takes, built from this one (bs_launch_kernel).
 struct BsLaunch : BsArgsEw {
     int word;                    // BsArgsXp::word
+    const int32_t* atid;         // BsArgsAf::atid (the pack-loop units' builds; null elsewhere)
     bool frozen;                 // host only: the plan equals BsFrozenWman (bs_frozen_fit) and the
                                  // request is a plain decode: launch the geometry-frozen build
     uint32_t* ticket;            // host only: the pack loop's ticket word (launch_bs_x), or null:
@@ -1891,9 +1930,15 @@ template <class K>
 K kernel_arg_of(void (*)(K));    // (the argument struct of a kernel, for decltype)
 // the kernel-argument struct K from the host's struct: that base of it (BsArgs, BsArgsEs,
 // BsArgsEw) or, for the export builds' K, the BsArgs base and the word switch; bsc's alike
+template <class K>
+struct BsAfBase { using type = void; };
+template <class K>
+struct BsAfBase<BsArgsAf<K>> { using type = K; };
 template <class K, class L>
 K bs_kernel_args(const L& a) {
     if constexpr (std::is_base_of_v<K, L>) return a;
+    else if constexpr (!std::is_void_v<typename BsAfBase<K>::type>)
+        return K{bs_kernel_args<typename BsAfBase<K>::type>(a), a.atid};
     else return K{a, a.word};
 }
 // every build may ask for all of BS_LDS_MAX as dynamic LDS: set once per kernel

@@ -1,5 +1,6 @@
 // ldpc_capi.hip — C ABI (include/ldpc_nms.h): graph/weights/context management, decode
 // dispatch, and the small compat kernels (output export, FER/BER counter finalisation).
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <functional>
@@ -7,6 +8,7 @@
 #include <vector>
 
 #include "ldpc_awgn.h"
+#include "ldpc_beta_tabs.h"
 #include "ldpc_internal.h"
 #include "ldpc_fused.h"
 
@@ -25,6 +27,7 @@ struct ldpc_graph {
     float* d_alpha_ucn = nullptr;
     float* d_beta = nullptr;
     int32_t* d_beta_tid = nullptr;   // [T][N] host::WeightInfo::beta_tid
+    int32_t* d_alpha_tid = nullptr;  // [T] host::WeightInfo::alpha_tid when every id is >= 0, else null
 };
 
 struct ldpc_ctx {
@@ -300,6 +303,7 @@ int ldpc_graph_destroy(ldpc_graph* g) {
     dev_free(g->d_alpha_ucn);
     dev_free(g->d_beta);
     dev_free(g->d_beta_tid);
+    dev_free(g->d_alpha_tid);
     dev_free(g->d_row_merge);
     delete g;
     return LDPC_OK;
@@ -331,13 +335,20 @@ int ldpc_weights_set(ldpc_graph* g, int32_t T, const float* alpha, const float* 
     dev_free(g->d_alpha_ucn);
     dev_free(g->d_beta);
     dev_free(g->d_beta_tid);
+    dev_free(g->d_alpha_tid);
     g->dev.beta_tid = nullptr;
+    g->h.w_alpha_tid_dev = nullptr;
     g->T_w = 0;
     const size_t ne = (size_t)T * g->h.E, nn = (size_t)T * g->h.N;
     int st = dev_alloc(&g->d_alpha, ne);
     if (st == LDPC_OK && alpha_ucn) st = dev_alloc(&g->d_alpha_ucn, ne);
     if (st == LDPC_OK) st = dev_alloc(&g->d_beta, nn);
     if (st == LDPC_OK) st = dev_alloc(&g->d_beta_tid, nn);
+    // the check tables' ids go up only when the whole weight set is in the fixed set: the one
+    // decision per weight set that the bit-sliced decode's check phase follows
+    const bool afix = !wi.alpha_tid.empty() &&
+                      std::all_of(wi.alpha_tid.begin(), wi.alpha_tid.end(), [](int32_t k) { return k >= 0; });
+    if (st == LDPC_OK && afix) st = dev_alloc(&g->d_alpha_tid, (size_t)T);
     if (st != LDPC_OK) return st;
     bool ok = hipMemcpy(g->d_alpha, alpha, ne * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
     if (alpha_ucn)
@@ -345,8 +356,11 @@ int ldpc_weights_set(ldpc_graph* g, int32_t T, const float* alpha, const float* 
                              hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && hipMemcpy(g->d_beta, beta, nn * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && hipMemcpy(g->d_beta_tid, wi.beta_tid.data(), nn * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
+    if (afix)
+        ok = ok && hipMemcpy(g->d_alpha_tid, wi.alpha_tid.data(), (size_t)T * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
     if (!ok) return LDPC_ERR_HIP;
     g->dev.beta_tid = g->d_beta_tid;
+    g->h.w_alpha_tid_dev = afix ? g->d_alpha_tid : nullptr;
     g->T_w = T;
     g->per_edge_w = wi.per_edge_w;
     g->row_merge = wi.row_merge;
@@ -978,6 +992,35 @@ int ldpc_debug_events_out(ldpc_ctx* c, const uint32_t* planes_dev, const uint32_
 int ldpc_ctx_last_frozen(const ldpc_ctx* c) {
     if (!c) return LDPC_ERR_ARG;
     return (c->fused.bs_frozen && std::strncmp(c->last_kernel, "bsl[", 4) == 0) ? 1 : 0;
+}
+
+// (include/ldpc_nms_debug.h) host::alpha_table_id and the ids host::analyze_weights gives a weight set
+extern "C" int ldpc_debug_alpha_tid(float alpha, int32_t mode, int32_t* out_id, uint8_t* table) {
+    if (!out_id) return LDPC_ERR_ARG;
+    const int k = host::alpha_table_id(alpha, mode);
+    *out_id = k;
+    if (k >= 0 && table) std::memcpy(table, kBetaTab[k], 16);
+    return LDPC_OK;
+}
+
+extern "C" int ldpc_debug_alpha_tids(const int32_t* proto, int32_t M, int32_t N, int32_t z, int32_t T, const float* alpha,
+                          const float* alpha_ucn, int32_t* ids) {
+    if (!proto || !alpha || !ids || T <= 0) return LDPC_ERR_ARG;
+    host::GraphTables h;
+    int st = host::build_graph(proto, M, N, z, h);
+    if (st != LDPC_OK) return st;
+    const std::vector<float> beta((size_t)T * h.N, 1.0f);
+    host::WeightInfo wi;
+    st = host::analyze_weights(h, T, alpha, alpha_ucn, beta.data(), wi);
+    if (st != LDPC_OK) return st;
+    if (wi.alpha_tid.empty()) return 0;
+    std::copy(wi.alpha_tid.begin(), wi.alpha_tid.end(), ids);
+    return 1;
+}
+
+int ldpc_ctx_last_afix(const ldpc_ctx* c) {
+    if (!c) return LDPC_ERR_ARG;
+    return (c->fused.bs_afix && std::strncmp(c->last_kernel, "bsl[", 4) == 0) ? 1 : 0;
 }
 
 int ldpc_ctx_last_kernel(const ldpc_ctx* c, char* name, int32_t name_len) {

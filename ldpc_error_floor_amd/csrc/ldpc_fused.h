@@ -25,6 +25,8 @@ struct FusedWorkspace {
     uint32_t* bs_ticket = nullptr; // the pack loop's ticket word (ldpc_bs_kernel.h, BS_RED_NEXT): allocated
                                    // at the first launch that wants it, zeroed before each one
     bool bs_frozen = false;        // the last bit-sliced decode ran a geometry-frozen build
+    bool bs_afix = false;          // the last bit-sliced decode weighed its check minima through the
+                                   // fixed-set tables (BsLaunch::atid set)
     uint32_t* hdx = nullptr;       // [T][packs][n_vars] bit-sliced hard decisions (bit export of
     int64_t hdx_elems = 0;         // the bit-sliced kernels; fixup packs are in `hd` instead)
     bool bits_packed = false;      // the last bit-exporting decode wrote hdx (+ hd for bad packs)

@@ -85,6 +85,29 @@ int beta_table_id(float b) {
     return -1;
 }
 
+// the 16-entry check table of k_bs_tables (ldpc_bs.hip) for one alpha on the grid of `step`, in
+// q_mag5's own float32 operations (ldpc_fused5_kernel.h): fl32(fl32(m step) alpha), relu, times
+// the inverse step, rint (half to even), clamped to 15
+static void alpha_table(float alpha, float step, uint8_t (&t)[16]) {
+    const float inv = 1.0f / step;
+    for (int m = 0; m < 16; ++m) {
+        const float mv = (float)m * step;
+        float x = mv * alpha;
+        x = (x > 0.f) ? x : 0.f;
+        const float r = std::nearbyint(x * inv);
+        t[m] = (uint8_t)std::min(std::max(r, -15.f), 15.f);     // (NaN cannot reach here: relu)
+    }
+}
+
+int alpha_table_id(float alpha, int mode) {
+    if (mode != MODE_Q5 && mode != MODE_QM5) return -1;
+    uint8_t t[16];
+    alpha_table(alpha, mode == MODE_Q5 ? 0.5f : 1.0f, t);
+    for (int k = 0; k < kNBetaTab; ++k)
+        if (std::equal(t, t + 16, kBetaTab[k])) return k;
+    return -1;
+}
+
 int analyze_weights(const GraphTables& g, int32_t T, const float* alpha, const float* alpha_ucn,
                     const float* beta, WeightInfo& w) {
     w = WeightInfo{};
@@ -152,6 +175,16 @@ int analyze_weights(const GraphTables& g, int32_t T, const float* alpha, const f
             if (b != b0) w.beta_uniform = 0;
             if (!(b >= 0.f)) w.beta_nonneg = 0;
             if (b != 1.f) w.beta_one = 0;
+        }
+    }
+    // one alpha per iteration: its check table's place in the fixed set, where the q = 5 and the
+    // q = -5 grid (both steps powers of two) give the same table, as they do short of underflow
+    if (w.alpha_uniform) {
+        w.alpha_tid.resize((size_t)T);
+        for (int t = 0; t < T; ++t) {
+            const float a0 = alpha[(size_t)t * g.E];
+            const int k = alpha_table_id(a0, MODE_Q5);
+            w.alpha_tid[(size_t)t] = (k == alpha_table_id(a0, MODE_QM5)) ? k : -1;
         }
     }
     return LDPC_OK;

@@ -55,6 +55,10 @@ struct GraphTables {
     // vn_edge [E] int4 {r0*z + (pe - r0), row degree, shift, (i*z) << 6 | (pe - r0)} in column order
     std::vector<int32_t> device_block;
     size_t off_vn = 0;               // int32 offset of vn_edge inside device_block
+    // Set by ldpc_weights_set for the graph's current weights, not by build_graph: the device copy
+    // of WeightInfo::alpha_tid [T] when every entry is >= 0, else null.  (Here, reached through
+    // DevGraph::host, and not in DevGraph, which is a kernel argument of the flood kernels.)
+    const int32_t* w_alpha_tid_dev = nullptr;
 };
 
 // LDPC_OK, LDPC_ERR_ARG (null / non-positive sizes / entry < -1 / no edge / sizes whose lifted
@@ -86,9 +90,18 @@ struct WeightInfo {
     // iteration t, min(15, |rint(fl32(m beta))|) for m = 0..15; -1 when beta < 0 or the table is
     // not in the set (the bit-sliced kernel then evaluates it from its table words)
     std::vector<int32_t> beta_tid;
+    // [T], filled when alpha is one value per iteration (alpha_uniform), else empty: index into
+    // kBetaTab of iteration t's q5 / q-5 check table Q(relu(alpha m)) for m = 0..15
+    // (alpha_table_id, the same id on both grids), -1 when the table is not in the set.  The
+    // bit-sliced kernel weighs the check minima through the fixed set only when all T are >= 0.
+    std::vector<int32_t> alpha_tid;
 };
 // kBetaTab index of beta's q5 / q-5 channel table, or -1
 int beta_table_id(float beta);
+// kBetaTab index of the check table the bit-sliced kernels build for alpha in `mode`
+// (k_bs_tables: Q(relu(fl32(fl32(m step) alpha))), m = 0..15), found by its content; -1 when
+// the table is not in the set or the mode is not MODE_Q5 / MODE_QM5
+int alpha_table_id(float alpha, int mode);
 int analyze_weights(const GraphTables& g, int32_t T, const float* alpha, const float* alpha_ucn,
                     const float* beta, WeightInfo& out);
 

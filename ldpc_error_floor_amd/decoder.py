@@ -715,6 +715,12 @@ class NMSDecoder:
         (``ldpc_ctx_last_frozen``; ``LDPC_BS_FROZEN=0`` forces the generic build)."""
         return False if self._ctx is None else bool(self._ext.last_frozen(self._ctx))
 
+    def last_afix(self) -> bool:
+        """Whether this decoder's last decode weighed the check minima of its bit-sliced kernel
+        through the fixed-set immediate tables (``ldpc_ctx_last_afix``; ``LDPC_BS_AFIX=0`` forces
+        the tables in LDS)."""
+        return False if self._ctx is None else bool(self._ext.last_afix(self._ctx))
+
     def _empty_result(self, T, nt, hard, synd, counters, flags, app, iter_wrong=False):
         """An empty batch decodes to empty outputs; a caller's counters are left unchanged."""
         torch = self._torch
