@@ -140,6 +140,14 @@ int ldpc_ctx_last_frozen(const ldpc_ctx* c);
    LDPC_BS_AFIX=0, read at every launch, forces the LDS tables. */
 int ldpc_ctx_last_afix(const ldpc_ctx* c);
 
+/* 1 when the last successful decode on this context ran a bit-sliced kernel ("bsl[...]") in a build
+   with the weights frozen in kind: a geometry-frozen build whose every check table and channel
+   table is one of the fixed set (or the identity channel table) and which reads their ids from LDS
+   (same name, same results); 0 when another build or kernel ran; LDPC_ERR_ARG for a null context.
+   The environment variable LDPC_BS_WF=0, read at every launch, forces the other builds; so do
+   LDPC_BS_AFIX=0, LDPC_BS_NOBFIX and LDPC_BS_FROZEN=0. */
+int ldpc_ctx_last_wf(const ldpc_ctx* c);
+
 /* On-GPU AWGN channel for the all-zero codeword (create_mix_epoch, Print_Functions.py:29-72):
    writes llr_dev [B][n_vars] f32 = Q(2(sigma*n - 1)/sigma^2) with punctured (1-based bits
    punct_start..punct_end, 0 = none) -> 0 and shortened -> -clip_llr.  Counter-based Philox

@@ -69,6 +69,19 @@ int ldpc_debug_alpha_tid(float alpha, int32_t mode, int32_t* out_id, uint8_t* ta
 int ldpc_debug_alpha_tids(const int32_t* proto, int32_t M, int32_t N, int32_t z, int32_t T,
                           const float* alpha, const float* alpha_ucn, int32_t* ids);
 
+/* The dispatch of the bit-sliced builds with the weights frozen in kind (csrc/ldpc_bs_kernel.h, WF)
+ * for a request of T iterations on a proto graph with a weight set of T_w >= T iterations (alpha,
+ * alpha_ucn or NULL [T_w][E], beta [T_w][N]); kind as for ldpc_debug_bs_frozen.  aids / bids [T]
+ * (or NULL) take the ids the launch hands its kernel: the check tables' and column 0 of the channel
+ * tables', -1 where it hands none of that kind; *identity (or NULL) the mask of the iterations
+ * whose channel table is the identity; alpha_tid_in [T_w] (or NULL) replaces the check ids the
+ * analysis found.  Returns 1 when such a build serves the request, 0 when not, or a negative
+ * status.  Honours LDPC_BS_WF, LDPC_BS_AFIX, LDPC_BS_NOBFIX and LDPC_BS_FROZEN as a launch does. */
+int ldpc_debug_bs_wf(const int32_t* proto, int32_t M, int32_t N, int32_t z, int32_t T_w,
+                     const float* alpha, const float* alpha_ucn, const float* beta, int32_t T,
+                     int32_t mode, int32_t kind, float clip, int32_t* aids, int32_t* bids,
+                     uint64_t* identity, const int32_t* alpha_tid_in);
+
 /* The event collector of ldpc_decode_events (csrc/ldpc_events.hip, events_out) on caller-supplied
  * device buffers instead of a decode's: planes_dev [ceil(B/32)][N*z], bit r of word (pack, v) =
  * variable v of frame 32 pack + r (the bits of a ragged last pack's frames past B may hold

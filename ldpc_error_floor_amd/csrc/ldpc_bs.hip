@@ -314,6 +314,34 @@ static bool bs_frozen_fit(const DevGraph& g, BsPlan& p, const BsReq& r, bool exp
     return true;
 }
 
+// How a launch of plan p weighs: bfix, the channel tables' ids go to the kernel (BsArgs::btid: the
+// grids whose magnitudes saturate at 15; LDPC_BS_NOBFIX keeps the table words); afix, the check
+// tables' ids do (BsArgsAf::atid: the pack-loop instances, one alpha per iteration, q = 5 / -5, and
+// every table of the weight set in the fixed set -- have_atid, one decision per weight set,
+// ldpc_weights_set; LDPC_BS_AFIX=0 keeps the tables in LDS); wf, the launch takes a build with the
+// weights frozen in kind (k_bs, WF): a frozen build would be taken, both kinds of ids go to the
+// kernel, and every one of the T channel tables is a table of the set, the same for all columns, or
+// the identity (GraphTables::w_wf_beta).  LDPC_BS_WF=0 keeps the other builds.  Every switch is read
+// at every launch.
+struct BsWeightPath { bool bfix, afix, wf; };
+static BsWeightPath bs_weight_path(const DevGraph& g, const BsPlan& p, const BsReq& r, bool frozen, bool have_atid) {
+    BsWeightPath w{false, false, false};
+    if (!p.ok) return w;
+    const BsInst& k = kBsInst[p.inst];
+    w.bfix = bs_qmax(r.mode) == QMAX && !getenv("LDPC_BS_NOBFIX");
+    if (bs_loops(k) && !p.ucn && p.arows == 1 && (r.mode == MODE_Q5 || r.mode == MODE_QM5)) {
+        const char* e = getenv("LDPC_BS_AFIX");
+        w.afix = (e ? atoi(e) != 0 : true) && have_atid;
+    }
+    const char* e = getenv("LDPC_BS_WF");
+    if (!frozen || !w.bfix || !w.afix || p.bcols != 1 || (e && atoi(e) == 0)) return w;
+    const std::vector<int32_t>& wb = g.host->w_wf_beta;
+    if ((int)wb.size() < r.T) return w;
+    w.wf = true;
+    for (int t = 0; t < r.T; ++t) w.wf = w.wf && wb[(size_t)t] >= 0;
+    return w;
+}
+
 // Deal `n` chunks (costs `cost`) to nw waves with at most `cap` chunks per wave (slot[w][c] =
 // chunk or -1; wave w runs on SIMD w mod 4).  The chunks of one phase end at a barrier, and a
 // SIMD's last busy wave runs alone, latency-bound (a dependent chain issues every ~8.5 cycles
@@ -876,18 +904,19 @@ static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const Bs
     a.arows = p.arows;
     a.bcols = p.bcols;
     // the fixed-set channel tables cover the grids whose magnitudes saturate at 15 (q = 5, -5)
-    a.btid = (bs_qmax(r.mode) == QMAX && !getenv("LDPC_BS_NOBFIX")) ? g.beta_tid : nullptr;
+    const BsWeightPath wp = bs_weight_path(g, p, r, frozen, g.host->w_alpha_tid_dev != nullptr);
+    a.btid = wp.bfix ? g.beta_tid : nullptr;
     a.btid_n = g.N;
     // the check tables' ids: the pack-loop instances, one alpha per iteration, the same grids, and
     // every table of the weight set in the fixed set (w_alpha_tid_dev is null otherwise: one decision
     // per weight set, ldpc_weights_set); LDPC_BS_AFIX=0, read at every launch like
     // LDPC_BS_TICKETS, keeps the tables in LDS
-    a.atid = nullptr;
-    if (bs_loops(k) && !p.ucn && p.arows == 1 && (r.mode == MODE_Q5 || r.mode == MODE_QM5)) {
-        const char* e = getenv("LDPC_BS_AFIX");
-        if (e ? atoi(e) != 0 : true) a.atid = g.host->w_alpha_tid_dev;
-    }
+    // (bs_weight_path; with both kinds of ids for all T iterations, a frozen launch takes the build
+    // with the weights frozen in kind)
+    a.atid = wp.afix ? g.host->w_alpha_tid_dev : nullptr;
     ws.bs_afix = a.atid != nullptr;
+    a.wf = wp.wf && a.atid != nullptr && a.btid != nullptr;
+    ws.bs_wf = a.wf;
     a.counters = o.counters;
     a.flags = o.flags;
     a.bad = o.bad;
@@ -930,7 +959,7 @@ static int bs_run(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const Bs
     const uint64_t rkey = (uint64_t)p.inst << 48 | (uint64_t)p.nw << 32 | (uint64_t)lds;
     if (ws.bs_resident_key != rkey) {
         ws.bs_resident_key = rkey;
-        std::fill(ws.bs_resident, ws.bs_resident + 7, 0);
+        std::fill(ws.bs_resident, ws.bs_resident + 9, 0);
     }
 #ifdef BS_STAMP
     // diagnostic build: per-wave phase clocks of this decode, printed to stderr
@@ -1000,6 +1029,7 @@ int bs_decode(const DevGraph& g, const Bufs& b, FusedWorkspace& ws, const float*
     BsPlan p = bs_route(g, r, &to_bsc);
     ws.bs_frozen = false;
     ws.bs_afix = false;
+    ws.bs_wf = false;
     if (!p.ok) return to_bsc ? bsc_decode(g, b, ws, llr, r, o, s) : LDPC_ERR_UNSUPPORTED;
     const bool frozen = bs_frozen_fit(g, p, r, o.hdx != nullptr || o.hdw != nullptr);
     return bs_run(g, b, ws, p, llr, r, o, frozen, s);
@@ -1225,6 +1255,57 @@ extern "C" int ldpc_debug_bs_frozen(const int32_t* proto, int32_t M, int32_t N, 
         names[names_len - 1] = 0;
     }
     return fz ? 1 : 0;
+}
+
+// The weights-frozen-in-kind dispatch (bs_weight_path) for a request on a proto graph with a weight
+// set [T_w] (alpha / alpha_ucn [T_w][E], beta [T_w][N]), host only: the weight set is analysed as
+// ldpc_weights_set does, the request planned and dispatched as bs_decode does.  kind as above.
+// aids / bids [T] take what the kernel is handed for iterations 0 .. T - 1: the check tables' ids
+// (BsArgsAf::atid) and column 0 of the channel tables' ids (BsArgs::btid; -1 where the launch hands
+// no ids of that kind).  *identity: the identity mask (BsArgs::beta_id).  alpha_tid_in [T_w], or
+// null: taken in place of the check ids the analysis found -- every alpha tried has its table in
+// the set (tests/test_bs_wf.py), so a set with one outside it can be stated only here.  Returns 1
+// when the launch takes a build with the weights frozen in kind, 0 when another, a negative status
+// on bad arguments.
+extern "C" int ldpc_debug_bs_wf(const int32_t* proto, int32_t M, int32_t N, int32_t z, int32_t T_w,
+                                const float* alpha, const float* alpha_ucn, const float* beta, int32_t T,
+                                int32_t mode, int32_t kind, float clip, int32_t* aids, int32_t* bids,
+                                uint64_t* identity, const int32_t* alpha_tid_in) {
+    using namespace ldpc;
+    using namespace ldpc::bs;
+    if (!proto || !alpha || !beta || T <= 0 || T > T_w || kind < 0 || kind > 2) return LDPC_ERR_ARG;
+    host::GraphTables h;
+    int st = host::build_graph(proto, M, N, z, h);
+    if (st != LDPC_OK) return st;
+    if (alpha_ucn && std::memcmp(alpha, alpha_ucn, (size_t)T_w * h.E * sizeof(float)) == 0) alpha_ucn = nullptr;
+    host::WeightInfo wi;
+    st = host::analyze_weights(h, T_w, alpha, alpha_ucn, beta, wi);
+    if (st != LDPC_OK) return st;
+    if (alpha_tid_in && !wi.alpha_tid.empty()) wi.alpha_tid.assign(alpha_tid_in, alpha_tid_in + T_w);
+    const bool have_atid = host::set_weight_ids(h, wi);
+    DevGraph g{};
+    g.M = h.M; g.N = h.N; g.z = h.z; g.E = h.E;
+    g.n_checks = h.M * h.z; g.n_vars = h.N * h.z; g.n_edges = h.E * h.z; g.max_cdeg = h.max_cdeg;
+    g.h_row_ptr = h.row_ptr.data();
+    g.host = &h;
+    g.w_alpha_uniform = wi.alpha_uniform;
+    g.w_alpha_pair_uniform = wi.alpha_pair_uniform;
+    g.w_beta_uniform = wi.beta_uniform;
+    g.w_beta_nonneg = wi.beta_nonneg;
+    g.w_beta_one = wi.beta_one;
+    g.w_beta_id_mask = wi.beta_id_mask;
+    g.w_ucn_iter = wi.ucn_iter_mask;
+    const BsReq r{mode, alpha_ucn != nullptr, wi.per_edge_w != 0, clip, T, kind == 1};
+    bool to_bsc;
+    BsPlan p = bs_route(g, r, &to_bsc);
+    const bool fz = bs_frozen_fit(g, p, r, kind == 2);
+    const BsWeightPath wp = bs_weight_path(g, p, r, fz, have_atid);
+    for (int t = 0; t < T; ++t) {
+        if (aids) aids[t] = wp.afix ? h.w_alpha_tid[(size_t)t] : -1;
+        if (bids) bids[t] = wp.bfix ? wi.beta_tid[(size_t)t * h.N] : -1;
+    }
+    if (identity) *identity = wi.beta_id_mask;
+    return wp.wf ? 1 : 0;
 }
 
 // One plan per (instance, UCN) that fits a proto graph with the given weight properties, each

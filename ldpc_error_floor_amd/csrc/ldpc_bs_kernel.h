@@ -642,6 +642,11 @@ using BsKernArgs = std::conditional_t<BS_LOOP_TU != 0, BsArgsAf<K>, K>;
 // the parked index is pack + gridDim.x, the fixed stride.  RED[8..15] are outside the per-pack
 // init (RED[12]: the stamp builds' SIMD of wave 0).
 constexpr int BS_RED_NEXT = 8;
+// The WF builds' id words (k_bs, WF), T words at the start of the alpha-table region of LDS, which
+// those builds leave unused: word t = the fixed-set id of iteration t's check table | the code of
+// iteration t + 1's channel table << 16 (the variable phase of iteration t forms |Q(beta_{t+1} ch)|;
+// the last takes none).  A channel table's code is its fixed-set id, or BS_WF_IDENT: the identity.
+constexpr int BS_WF_IDENT = kNBetaTab;
 // what a pack (index pk) derives from the arguments alone: at the kernel's entry with one pack
 // per workgroup, at each pack's top in the pack loop.  RED: [0] wrong_t, [1] all t, [2] APP > 0,
 // [3] bits; flor: the FLORW OR words; ALUT [2][AR][LUT_W], BLUT [2][bcols][BLUT_W];
@@ -680,7 +685,7 @@ constexpr int BS_RED_NEXT = 8;
 // iteration; a pack leaves the T loop once each of its codewords has had a zero syndrome, and the
 // epilogue takes every codeword's outputs at its own first zero-syndrome iteration.
 template <int D, int DV, int LPC, int VPL, int CPL, bool UCN, bool BIG, bool PK, int WPE, bool XP, int LB, bool Q8,
-          bool ES = false, bool EW = false, bool FZ = false, bool L8 = false>
+          bool ES = false, bool EW = false, bool FZ = false, bool L8 = false, bool WF = false>
 __global__ void __launch_bounds__(LB) __attribute__((amdgpu_waves_per_eu(WPE)))
 k_bs(BsKernArgs<std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::conditional_t<XP, BsArgsXp, BsArgs>>> a) {
     static_assert(LPC == 2 || LPC == 4, "lanes per check");
@@ -733,6 +738,17 @@ k_bs(BsKernArgs<std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs
     // launch gives their ids (BsArgsAf::atid): the pack-loop units
     constexpr bool AFX = BS_LOOP_TU != 0;
     static_assert(!AFX || (ONE && !UCN), "fixed-set check tables: the one-chunk instances without UCN");
+    // WF: the weights frozen in kind: every iteration's check table and channel table
+    // is a table of the fixed set (or the identity channel table), so the build has no other path
+    // for either -- no table words in LDS or SGPRs, no table copies, no tests of the ids' pointers --
+    // and its T loop reads the ids from LDS words (BS_WF_* below), not from scalar memory: a scalar
+    // load's result returns out of order, so each use of one waits for lgkmcnt(0), which also drains
+    // the slot reads in flight.  The host takes it only when all T ids of both kinds exist
+    // (ldpc_bs.hip, bs_weight_path); builds of the geometry-frozen decode and in-prologue channel
+    // builds of wman.
+    static_assert(!WF || (FZ && AFX && !BIG && !L8), "weights frozen in kind: on the geometry-frozen builds");
+    // (the variable phase's channel code comes out of the check phase's id word: every wave runs it)
+    static_assert(!WF || BsFrozenWman::cn_lanes >= BsFrozenWman::NT, "weights frozen in kind: every wave holds check lanes");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if ((uint32_t)(uintptr_t)smem != 0u) __builtin_trap();          // slots are LDS-absolute
 #ifdef BS_STAMP
@@ -925,7 +941,7 @@ k_bs(BsKernArgs<std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs
     BS_ST(8);
     uint32_t cs[VPL], cm[VPL][4], bg[VPL];
     int off = 0;
-    if (T0A) {                           // (retired by the channel barrier's vmcnt(0))
+    if (T0A && !WF) {                    // (retired by the channel barrier's vmcnt(0); WF: no table words)
         copy_async((FZ ? W::off_alut : a.off_alut), a.alut, AL, wave, NT);
         copy_async((FZ ? W::off_blut : a.off_blut), a.blut, BL, wave, NT);
     }
@@ -1105,11 +1121,31 @@ k_bs(BsKernArgs<std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs
     int bkp[VPL];                        // (BKPF) the ids of iteration tb's tables, loaded early
 #pragma unroll
     for (int u = 0; u < VPL; ++u) bkp[u] = -1;
+    // (WF) the code of the channel table the next variable phase takes (BS_WF_IDENT: the identity),
+    // wave-uniform: iteration 0's from the arguments here, in the prologue; iteration t + 1's from
+    // check phase t's id word
+    [[maybe_unused]] int wf_bk = 0;
+    if constexpr (WF) {
+        wf_bk = (a.beta_id & 1) ? BS_WF_IDENT
+                                : __builtin_amdgcn_readfirstlane((int)((const ConstW*)a.btid)[0]);
+    }
     // |Q(beta_tb ch)| (4 planes) of the lane's variable u: the identity table, one of the fixed
     // set (wave-uniform id: a jump into immediate truth tables), the iteration's table in
     // constant memory (one beta per iteration) or the LDS table words (bslice)
     auto beta_lw = [&](const int u, const uint32_t bslice, const int tb, const uint32_t (&cmu)[4],
                        uint32_t (&lw)[4], const bool use_bk) __attribute__((always_inline)) {
+        if constexpr (WF) {
+            // the table's code (wave-uniform, wf_bk): the identity, or a table of the fixed set
+            if (ABL(2) || wf_bk >= BS_WF_IDENT) {
+                PH("vn_beta_id", u);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) lw[i] = cmu[i];
+            } else {
+                PH("vn_beta_fix", u);
+                beta_asm(lw, cmu, wf_bk);
+            }
+            return;
+        }
         int bk = -1;
         if constexpr (!XP) {
             if (use_bk && a.btid) {
@@ -1350,6 +1386,22 @@ k_bs(BsKernArgs<std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs
 
     vn_phase(true, false, (FZ ? W::off_blut : a.off_blut), 0);
     BS_ST(12);
+    // (WF) the pack's id words (BS_WF_IDENT above), one per lane of the first T: loaded here, beside
+    // the check setup's own global loads, and stored with its per-lane words ahead of the T loop's
+    // barrier.  The region is written nowhere else.  The pack before read its last id word in check
+    // phase T - 1, and the barriers after that check phase and its variable phase, and the one at
+    // this pack's top, lie between that read and this store; besides, every pack of a launch
+    // writes the same words.  Words that differed from pack to pack would rest on those barriers
+    // alone.
+    [[maybe_unused]] uint32_t wf_idw = 0u;
+    if constexpr (WF) {
+        if (tid < a.T) {
+            wf_idw = (uint32_t)kern_args<BsArgsAf<KArgs>>().atid[tid];
+            if (tid + 1 < a.T)
+                wf_idw |= (((a.beta_id >> (tid + 1)) & 1) ? (uint32_t)BS_WF_IDENT
+                                                          : (uint32_t)a.btid[(size_t)(tid + 1) * W::btid_n]) << 16;
+        }
+    }
     // check groups: chunk k of 64 check lanes; lane LPC c + j of it (check c = row i, index h)
     // takes edges k = LPC m + j, at slots first_i + j A_i + m z + h (a.row_lay); edges past the
     // degree read the all-ones PAD slot and are not written; idle lanes (c >= n_checks) read PAD
@@ -1404,6 +1456,9 @@ k_bs(BsKernArgs<std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs
     // one LDS word per lane and read at each check phase, not in a register held through the T loop
     constexpr bool GBL = CPL == 1;
     if constexpr (GBL) lds_put((FZ ? W::off_ch : a.off_ch) + 4u * (uint32_t)tid, gbase[0]);
+    if constexpr (WF) {
+        if (tid < a.T) lds_put(W::off_alut + 4u * (uint32_t)tid, wf_idw);
+    }
     // the one-chunk UCN instances' packed hard-decision addresses (HDW words per check lane)
     // likewise in LDS, read at each check phase
     constexpr bool HDL = UCN && CPL == 1;
@@ -1437,7 +1492,8 @@ k_bs(BsKernArgs<std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs
         // launch-uniform choice.
         int ak = 0;
         bool afx = false;
-        if constexpr (AFX) {
+        // (WF: no scalar load in the loop -- the check phase reads the id word from LDS)
+        if constexpr (AFX && !WF) {
             typedef __attribute__((address_space(4))) const BsArgsAf<KArgs> ConstAf;
             ConstAf* kq = (ConstAf*)__builtin_amdgcn_kernarg_segment_ptr();
             asm volatile("" : "+s"(kq));
@@ -1459,37 +1515,40 @@ k_bs(BsKernArgs<std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs
         // next iteration's tables (their slots were last read two phases ago), copied global ->
         // LDS asynchronously: no wave waits for the loads, the barrier after the check phase
         // retires them
-        if (t + 1 < a.T) {
-            // the copies' wave-uniform bounds made opaque per iteration, so their compares are
-            // redone here instead of held through the loop as 64-bit lane masks (not in wman's
-            // in-prologue channel build, which ran slower with it)
-            int cw = wave, al = AL, bl = BL, bcl = (FZ ? W::bcols : a.bcols);
-            // (the frozen builds: the bounds are literals.  The copy loop itself stays: a one-trip
-            // form of it, or the wave count given to the compiler, each brought a VGPR spill back)
-            if (!FZ && !(Q8 && VPL == 1 && CPL == 1 && !UCN))
-                asm volatile("" : "+s"(cw), "+s"(al), "+s"(bl), "+s"(bcl));
-            // the tables' addresses loaded again from the kernel arguments each iteration (scalar
-            // loads) instead of held through the loop, where they were spilled to VGPR lanes: the
-            // one-chunk instances but wman's in-prologue channel build
-            const uint32_t* alut_p = a.alut;
-            const uint32_t* blut_p = a.blut;
-            uint32_t off_al = (FZ ? W::off_alut : a.off_alut), off_bl = (FZ ? W::off_blut : a.off_blut);
-            if constexpr (VPL == 1 && CPL == 1 && !(Q8 && !UCN)) {
-                typedef __attribute__((address_space(4))) const BsArgs ConstArgs;
-                ConstArgs* ka = (ConstArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-                asm volatile("" : "+s"(ka));
-                alut_p = ka->alut;
-                blut_p = ka->blut;
-                if constexpr (!FZ) {
-                    off_al = ka->off_alut;
-                    off_bl = ka->off_blut;
+        // (WF: no table words at all, so neither copy nor the tables' pointers)
+        if constexpr (!WF) {
+            if (t + 1 < a.T) {
+                // the copies' wave-uniform bounds made opaque per iteration, so their compares are
+                // redone here instead of held through the loop as 64-bit lane masks (not in wman's
+                // in-prologue channel build, which ran slower with it)
+                int cw = wave, al = AL, bl = BL, bcl = (FZ ? W::bcols : a.bcols);
+                // (the frozen builds: the bounds are literals.  The copy loop itself stays: a one-trip
+                // form of it, or the wave count given to the compiler, each brought a VGPR spill back)
+                if (!FZ && !(Q8 && VPL == 1 && CPL == 1 && !UCN))
+                    asm volatile("" : "+s"(cw), "+s"(al), "+s"(bl), "+s"(bcl));
+                // the tables' addresses loaded again from the kernel arguments each iteration (scalar
+                // loads) instead of held through the loop, where they were spilled to VGPR lanes: the
+                // one-chunk instances but wman's in-prologue channel build
+                const uint32_t* alut_p = a.alut;
+                const uint32_t* blut_p = a.blut;
+                uint32_t off_al = (FZ ? W::off_alut : a.off_alut), off_bl = (FZ ? W::off_blut : a.off_blut);
+                if constexpr (VPL == 1 && CPL == 1 && !(Q8 && !UCN)) {
+                    typedef __attribute__((address_space(4))) const BsArgs ConstArgs;
+                    ConstArgs* ka = (ConstArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+                    asm volatile("" : "+s"(ka));
+                    alut_p = ka->alut;
+                    blut_p = ka->blut;
+                    if constexpr (!FZ) {
+                        off_al = ka->off_alut;
+                        off_bl = ka->off_blut;
+                    }
                 }
+                // (no alpha table where the check phase takes the fixed set's: its LDS region stays unused)
+                if (!(AFX && afx))
+                    copy_async(off_al + 4u * (uint32_t)(nx * al), alut_p + (size_t)(t + 1) * al, al, cw, NT);
+                if (bcl > 1)
+                    copy_async(off_bl + 4u * (uint32_t)(nx * bl), blut_p + (size_t)(t + 1) * bl, bl, cw, NT);
             }
-            // (no alpha table where the check phase takes the fixed set's: its LDS region stays unused)
-            if (!(AFX && afx))
-                copy_async(off_al + 4u * (uint32_t)(nx * al), alut_p + (size_t)(t + 1) * al, al, cw, NT);
-            if (bcl > 1)
-                copy_async(off_bl + 4u * (uint32_t)(nx * bl), blut_p + (size_t)(t + 1) * bl, bl, cw, NT);
         }
         if constexpr (BKPF) {                // this iteration's variable phase: ids of row t + 1
             if (t + 1 < a.T && a.btid) {     // (the last variable phase takes no table)
@@ -1520,6 +1579,10 @@ k_bs(BsKernArgs<std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs
                 cbase = gbase[c];
                 asm volatile("" : "+v"(cbase));
             }
+            // (WF) iteration t's id word: every lane the same address, a broadcast read issued with
+            // the slot base's, made wave-uniform after the minima search
+            [[maybe_unused]] uint32_t idw = 0u;
+            if constexpr (WF) idw = lds_w(W::off_alut + 4u * (uint32_t)t);
             uint32_t ctab = PKG ? (cbase >> 16) : gtab[c];
             if constexpr (PKG) cbase &= 0xFFFFu;
             int gmc = gm[c];
@@ -1634,6 +1697,14 @@ k_bs(BsKernArgs<std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs
             // weighted, quantized minima: each lane evaluates OB output bits, the group shares them
             uint32_t q1[4], q2[4];
             PH9("ck_tab", c, m1, m2, par);
+            if constexpr (WF) {
+                // both minima through the immediate truth tables of the id word's check table; its
+                // upper half is the code of the channel table this iteration's variable phase takes
+                const uint32_t iw = (uint32_t)__builtin_amdgcn_readfirstlane((int)idw);
+                wf_bk = (int)(iw >> 16);
+                beta_asm(q1, m1, (int)(iw & 0xFFFFu));
+                beta_asm(q2, m2, (int)(iw & 0xFFFFu));
+            } else
             if (AFX && afx) {
                 // alpha_t's table is table ak of the fixed set: both minima of the group, which
                 // every lane of it holds, through the immediate truth tables -- all four planes in
@@ -1922,6 +1993,8 @@ struct BsLaunch : BsArgsEw {
     const int32_t* atid;         // BsArgsAf::atid (the pack-loop units' builds; null elsewhere)
     bool frozen;                 // host only: the plan equals BsFrozenWman (bs_frozen_fit) and the
                                  // request is a plain decode: launch the geometry-frozen build
+    bool wf;                     // host only: of the frozen builds, the one with the weights frozen in
+                                 // kind (k_bs, WF): atid and btid hold all T ids (bs_weight_path)
     uint32_t* ticket;            // host only: the pack loop's ticket word (launch_bs_x), or null:
                                  // fixed stride (LDPC_BS_TICKETS=0)
 };
@@ -1960,11 +2033,11 @@ int bs_launch_kernel(const L& a, int nblocks, int nw, size_t lds, hipStream_t s)
 // to the packs, the others exactly one per pack.  *resident (ldpc_bs.hip: one word per context and
 // build): the workgroups of this instance, workgroup size and LDS size that fit the device at
 // once, asked from the runtime when it is 0.
-template <int I, bool XP, bool Q8, bool FZ = false, bool L8 = false>
+template <int I, bool XP, bool Q8, bool FZ = false, bool L8 = false, bool WF = false>
 int launch_bs_x(const BsLaunch& a, int npacks, int nw, size_t lds, hipStream_t s, int grid, int* resident) {
     constexpr BsInst k = kBsInst[I];
     static_assert(bs_loops(k) == (BS_LOOP_TU != 0), "BS_LOOP_TU lists the instances of bs_loops");
-    constexpr auto fn = &k_bs<k.D, k.DV, k.LPC, k.VPL, k.CPL, k.UCN, k.BIG, k.PK, k.WPE, XP, 1024, Q8, false, false, FZ, L8>;
+    constexpr auto fn = &k_bs<k.D, k.DV, k.LPC, k.VPL, k.CPL, k.UCN, k.BIG, k.PK, k.WPE, XP, 1024, Q8, false, false, FZ, L8, WF>;
     int nblocks = npacks;
     if constexpr (bs_loops(k)) {
         if (grid < 0) {                      // (no LDPC_BS_GRID: the resident workgroups)
@@ -2033,8 +2106,12 @@ int launch_bs_any(const BsLaunch& a, int npacks, int nw, size_t lds, hipStream_t
     } else {
         // (the generated channel comes from ldpc_decode_awgn, which exports no hard bits)
         // (resident[0 / 1 / 2]: the decode, the hard-bit export and the in-prologue channel build;
-        // [3 / 4]: the geometry-frozen decode and in-prologue channel builds)
+        // [3 / 4]: the geometry-frozen decode and in-prologue channel builds; [7 / 8]: the same two
+        // with the weights frozen in kind)
         if constexpr (I == BsFrozenWman::inst) {
+            if (a.frozen && a.wf && !a.hdx)
+                return q8 ? launch_bs_x<I, false, true, true, false, true>(a, npacks, nw, lds, s, grid, resident + 8)
+                          : launch_bs_x<I, false, false, true, false, true>(a, npacks, nw, lds, s, grid, resident + 7);
             if (a.frozen && !a.hdx)
                 return q8 ? launch_bs_x<I, false, true, true>(a, npacks, nw, lds, s, grid, resident + 4)
                           : launch_bs_x<I, false, false, true>(a, npacks, nw, lds, s, grid, resident + 3);

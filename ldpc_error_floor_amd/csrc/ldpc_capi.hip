@@ -346,8 +346,7 @@ int ldpc_weights_set(ldpc_graph* g, int32_t T, const float* alpha, const float* 
     if (st == LDPC_OK) st = dev_alloc(&g->d_beta_tid, nn);
     // the check tables' ids go up only when the whole weight set is in the fixed set: the one
     // decision per weight set that the bit-sliced decode's check phase follows
-    const bool afix = !wi.alpha_tid.empty() &&
-                      std::all_of(wi.alpha_tid.begin(), wi.alpha_tid.end(), [](int32_t k) { return k >= 0; });
+    const bool afix = host::set_weight_ids(g->h, wi);
     if (st == LDPC_OK && afix) st = dev_alloc(&g->d_alpha_tid, (size_t)T);
     if (st != LDPC_OK) return st;
     bool ok = hipMemcpy(g->d_alpha, alpha, ne * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
@@ -1021,6 +1020,11 @@ extern "C" int ldpc_debug_alpha_tids(const int32_t* proto, int32_t M, int32_t N,
 int ldpc_ctx_last_afix(const ldpc_ctx* c) {
     if (!c) return LDPC_ERR_ARG;
     return (c->fused.bs_afix && std::strncmp(c->last_kernel, "bsl[", 4) == 0) ? 1 : 0;
+}
+
+int ldpc_ctx_last_wf(const ldpc_ctx* c) {
+    if (!c) return LDPC_ERR_ARG;
+    return (c->fused.bs_wf && std::strncmp(c->last_kernel, "bsl[", 4) == 0) ? 1 : 0;
 }
 
 int ldpc_ctx_last_kernel(const ldpc_ctx* c, char* name, int32_t name_len) {

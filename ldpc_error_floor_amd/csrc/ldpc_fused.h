@@ -19,14 +19,18 @@ struct FusedWorkspace {
     size_t bs_lut_bytes = 0;
     uint32_t* bs_bad = nullptr;    // [packs] 1: pack decoded by the v5 fixup
     int64_t bs_bad_n = 0;
-    int bs_resident[7] = {0, 0, 0, 0, 0, 0, 0};   // bit-sliced kernel with the pack loop: the workgroups resident
+    int bs_resident[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // bit-sliced kernel with the pack loop: the workgroups resident
     uint64_t bs_resident_key = ~0ull; // at once (decode / export / channel build, the frozen decode /
-                                      // channel build, the int8 decode / word build), and what for
+                                      // channel build, the int8 decode / word build, the frozen
+                                      // decode / channel build with the weights frozen in kind), and
+                                      // what for
     uint32_t* bs_ticket = nullptr; // the pack loop's ticket word (ldpc_bs_kernel.h, BS_RED_NEXT): allocated
                                    // at the first launch that wants it, zeroed before each one
     bool bs_frozen = false;        // the last bit-sliced decode ran a geometry-frozen build
     bool bs_afix = false;          // the last bit-sliced decode weighed its check minima through the
                                    // fixed-set tables (BsLaunch::atid set)
+    bool bs_wf = false;            // the last bit-sliced decode ran a build with the weights frozen in
+                                   // kind (BsLaunch::wf)
     uint32_t* hdx = nullptr;       // [T][packs][n_vars] bit-sliced hard decisions (bit export of
     int64_t hdx_elems = 0;         // the bit-sliced kernels; fixup packs are in `hd` instead)
     bool bits_packed = false;      // the last bit-exporting decode wrote hdx (+ hd for bad packs)

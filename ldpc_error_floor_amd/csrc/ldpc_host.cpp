@@ -166,6 +166,13 @@ int analyze_weights(const GraphTables& g, int32_t T, const float* alpha, const f
                 }
     w.beta_tid.resize((size_t)T * g.N);
     for (size_t x = 0; x < (size_t)T * g.N; ++x) w.beta_tid[x] = beta_table_id(beta[x]);
+    w.wf_beta.assign((size_t)T, -1);
+    for (int t = 0; t < T; ++t) {
+        int32_t k = w.beta_tid[(size_t)t * g.N];
+        for (int j = 1; j < g.N; ++j)
+            if (w.beta_tid[(size_t)t * g.N + j] != k) k = -1;
+        w.wf_beta[(size_t)t] = (t < 64 && ((w.beta_id_mask >> t) & 1)) ? kNBetaTab : k;
+    }
     for (int t = 0; t < T; ++t) {
         const float a0 = alpha[(size_t)t * g.E], b0 = beta[(size_t)t * g.N];
         for (int e = 1; e < g.E && w.alpha_uniform; ++e)

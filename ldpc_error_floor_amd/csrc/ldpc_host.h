@@ -59,6 +59,10 @@ struct GraphTables {
     // of WeightInfo::alpha_tid [T] when every entry is >= 0, else null.  (Here, reached through
     // DevGraph::host, and not in DevGraph, which is a kernel argument of the flood kernels.)
     const int32_t* w_alpha_tid_dev = nullptr;
+    // Likewise set for the current weights (set_weight_ids): the host's copy of those ids, empty
+    // unless every entry is >= 0, and WeightInfo::wf_beta -- what the bit-sliced decode's choice of
+    // a build with the weights frozen in kind reads (ldpc_bs.hip, bs_weight_path).
+    std::vector<int32_t> w_alpha_tid, w_wf_beta;
 };
 
 // LDPC_OK, LDPC_ERR_ARG (null / non-positive sizes / entry < -1 / no edge / sizes whose lifted
@@ -95,6 +99,11 @@ struct WeightInfo {
     // (alpha_table_id, the same id on both grids), -1 when the table is not in the set.  The
     // bit-sliced kernel weighs the check minima through the fixed set only when all T are >= 0.
     std::vector<int32_t> alpha_tid;
+    // [T]: iteration t's channel table as the bit-sliced builds with the weights frozen in kind take
+    // it (ldpc_bs_kernel.h, WF) -- kNBetaTab where the table is the identity (bit t of
+    // beta_id_mask), else column 0's beta_tid where every column has that same id, else -1 (a
+    // table outside the set, a negative beta, or columns that differ)
+    std::vector<int32_t> wf_beta;
 };
 // kBetaTab index of beta's q5 / q-5 channel table, or -1
 int beta_table_id(float beta);
@@ -104,6 +113,15 @@ int beta_table_id(float beta);
 int alpha_table_id(float alpha, int mode);
 int analyze_weights(const GraphTables& g, int32_t T, const float* alpha, const float* alpha_ucn,
                     const float* beta, WeightInfo& out);
+// the graph's host-side ids of a weight set (GraphTables::w_alpha_tid, w_wf_beta); true when the
+// check tables' ids exist, i.e. when ldpc_weights_set uploads them
+inline bool set_weight_ids(GraphTables& g, const WeightInfo& w) {
+    bool all = !w.alpha_tid.empty();
+    for (const int32_t k : w.alpha_tid) all = all && k >= 0;
+    g.w_alpha_tid = all ? w.alpha_tid : std::vector<int32_t>();
+    g.w_wf_beta = w.wf_beta;
+    return all;
+}
 
 // ldpc_decode / ldpc_decode_awgn argument checks.  Returns LDPC_OK and the mode, or the status
 // the ABI reports: LDPC_ERR_ARG (null params, bad mode, target_bits, clip_llr, kernel) or

@@ -595,6 +595,14 @@ PYBIND11_MODULE(_ldpc_nms, m) {
         },
         py::arg("ctx"));
     m.def(
+        "last_wf",
+        [](Ctx& c) {
+            const int r = ldpc_ctx_last_wf(c.h);
+            check(r < 0 ? r : 0, "ldpc_ctx_last_wf");
+            return r == 1;
+        },
+        py::arg("ctx"));
+    m.def(
         "format_uncor_rows",
         [](py::array_t<float, py::array::c_style | py::array::forcecast> rows) {
             if (rows.ndim() != 2 || rows.shape(1) <= 0)

@@ -721,6 +721,11 @@ class NMSDecoder:
         the tables in LDS)."""
         return False if self._ctx is None else bool(self._ext.last_afix(self._ctx))
 
+    def last_wf(self) -> bool:
+        """Whether this decoder's last decode ran a bit-sliced build with the weights frozen in
+        kind (``ldpc_ctx_last_wf``; ``LDPC_BS_WF=0`` forces the other builds)."""
+        return False if self._ctx is None else bool(self._ext.last_wf(self._ctx))
+
     def _empty_result(self, T, nt, hard, synd, counters, flags, app, iter_wrong=False):
         """An empty batch decodes to empty outputs; a caller's counters are left unchanged."""
         torch = self._torch
