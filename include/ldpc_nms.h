@@ -404,6 +404,32 @@ int ldpc_decode_q8_word(ldpc_ctx* ctx, const int8_t* q8_dev, int64_t B, const ld
    status. */
 int ldpc_q8_supported(const ldpc_ctx* ctx, const ldpc_decode_params* params, int32_t has_short,
                       int32_t word);
+/* int8 LLRs in the early-stop, stop-iteration-word and events modes: q8_dev as
+   above.  For every valid q8, every output equals, bit for bit, that of the float entry point of
+   the same kind -- ldpc_decode_es, ldpc_decode_es_word, ldpc_decode_events -- on the float LLRs
+   the bytes stand for.  A pack of 32 codewords holding an invalid byte in one of its codewords is
+   not decoded, as in those modes a pack off the grid is not: frame_flags = 0x80, n_iter = 0
+   (hard_stop rows zero, word_flags = 0x80, no event), nothing in the counters or in iter_hist.
+   ldpc_decode_q8_events serves both values of outputs->early_stop: 1 decodes with the int8
+   early-stop builds, 0 with the int8 word build of ldpc_decode_q8_word (served where
+   ldpc_q8_supported with word = 1 is).
+   A NULL q8_dev, a wrong struct size or a missing required pointer (hard_stop; ev_count, ev_frame,
+   ev_info, cap < 0) is LDPC_ERR_ARG before the context is read.  Served where the float entry
+   point is served and the plan's early-stop instance has the int8 builds (bsl: wman, 802.11n;
+   bsc: the beta = 1 builds); anything else is LDPC_ERR_UNSUPPORTED with nothing launched or
+   written.  ldpc_ctx_last_kernel reports the float mode's name and "+q8": "bsl[...,es]+q8",
+   "bsl[...,es,word]+q8", "bsl[...,es,events]+q8", "bsl[...,events]+q8", the "bsc[...]" forms
+   likewise. */
+int ldpc_decode_q8_es(ldpc_ctx* ctx, const int8_t* q8_dev, int64_t B, const ldpc_decode_params* params,
+                      const ldpc_es_outputs* es_outputs, void* stream);
+int ldpc_decode_q8_es_word(ldpc_ctx* ctx, const int8_t* q8_dev, int64_t B, const ldpc_decode_params* params,
+                           const ldpc_es_word_outputs* es_word_outputs, void* stream);
+int ldpc_decode_q8_events(ldpc_ctx* ctx, const int8_t* q8_dev, int64_t B, const ldpc_decode_params* params,
+                          const ldpc_event_outputs* outputs, void* stream);
+/* Whether the early-stop entry points above (ldpc_decode_q8_es, ldpc_decode_q8_es_word,
+   ldpc_decode_q8_events with early_stop = 1) serve these parameters on this context, for input
+   with (has_short = 1) or without the +-clip markers: 1, 0, or a negative status. */
+int ldpc_q8_es_supported(const ldpc_ctx* ctx, const ldpc_decode_params* params, int32_t has_short);
 /* ldpc_channel_awgn's QMS channel as int8 rows (q8_dev [B][n_vars]): the same Philox stream and
    level sampler, so the bytes equal ldpc_llr_to_q8 of ldpc_channel_awgn's output; punctured bits
    0, shortened bits -128.  QMS with q_bit 5, -5, 4 or 3 only (else LDPC_ERR_UNSUPPORTED). */

@@ -828,10 +828,10 @@ bool bs_q8_ok(const DevGraph& g, const BsReq& r, bool has_short) {
 
 bool bs_l8_ok(const DevGraph& g, const BsReq& r, bool has_short) {
     bool to_bsc;
-    if (r.es) return false;
     const BsPlan p = bs_route(g, r, &to_bsc);
     if (!p.ok) return to_bsc && bsc_l8_ok(g, r, has_short);
-    return bs_l8_inst(p.inst) && (!has_short || (kBsInst[p.inst].BIG && p.cu > 0.f));
+    // (an early-stop request's plan is an ES instance's, and each of those has its int8 builds)
+    return (r.es ? kBsInst[p.inst].ES : bs_l8_inst(p.inst)) && (!has_short || (kBsInst[p.inst].BIG && p.cu > 0.f));
 }
 
 const char* bs_kernel_name(const DevGraph& g, const BsReq& r) {

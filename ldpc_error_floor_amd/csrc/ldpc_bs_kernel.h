@@ -679,7 +679,8 @@ constexpr int BS_WF_IDENT = kNBetaTab;
 // EW: the early-stop build that also keeps each codeword's hard decisions at its stop iteration
 // (DESIGN 3.9): a build of its own beside the ES build, which stays as it is.
 // L8: the LLRs read as int8 grid values (a.llr points at bytes: ldpc_decode_q8), a
-// build of its own for the reason Q8 is one; a pack with an invalid byte is marked, never fixed up
+// build of its own for the reason Q8 is one; a pack with an invalid byte is marked, never fixed up;
+// with ES / EW the int8 builds of the early-stop kernels (ldpc_decode_q8_es)
 // ES: the early-stop build (one-chunk UCN-compiled instances, one pack per
 // workgroup).  The hard decisions go to HD and the check phases take their syndromes at every
 // iteration; a pack leaves the T loop once each of its codewords has had a zero syndrome, and the
@@ -692,7 +693,7 @@ k_bs(BsKernArgs<std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs
     using KArgs = std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs>, std::conditional_t<XP, BsArgsXp, BsArgs>>;
     static_assert(!ES || (UCN && VPL == 1 && CPL == 1 && !XP), "early stop: one-chunk UCN-compiled instances");
     static_assert(!EW || ES, "the stop-iteration word: early-stop builds");
-    static_assert(!L8 || (!Q8 && !ES && !FZ), "int8 LLRs: the decode and export builds");
+    static_assert(!L8 || (!Q8 && !FZ), "int8 LLRs: the decode, export and early-stop builds");
     // FZ: the geometry-frozen build (ldpc_bs_frozen.h): the pack geometry is W's literals instead
     // of kernel arguments, (FZ ? W::x : a.x) at each read -- written out, not behind an accessor:
     // through one the other builds' code changed; the pack-loop decode and in-prologue channel
@@ -1098,8 +1099,9 @@ k_bs(BsKernArgs<std::conditional_t<ES, std::conditional_t<EW, BsArgsEw, BsArgsEs
                 if (kern_args<KArgs>().n_iter) kern_args<KArgs>().n_iter[b0 + tid] = 0;
             }
         }
-        if constexpr (L8) {
+        if constexpr (L8 && !ES) {
             // int8 LLRs: an invalid byte has no float decode to fall back to; marked the same way
+            // (the early-stop int8 builds: by the block above, once)
             if (tid < nvalid && a.flags) a.flags[b0 + tid] = 0x80;
         }
         if (tid == 0) a.bad[BS_PK] = 1u;
@@ -2070,17 +2072,19 @@ int launch_bs_x(const BsLaunch& a, int npacks, int nw, size_t lds, hipStream_t s
 
 // the early-stop builds of an ES instance (float LLRs, or the in-prologue channel): one workgroup
 // per pack, no pack loop (packs end at different times) and no export build
-template <int I, bool Q8, bool EW>
+// (L8: the int8-LLR builds of the two; launched the same way)
+template <int I, bool Q8, bool EW, bool L8 = false>
 int launch_bs_es_x(const BsLaunch& a, int npacks, int nw, size_t lds, hipStream_t s) {
     constexpr BsInst k = kBsInst[I];
     static_assert(k.ES && !bs_loops(k), "an early-stop instance");
-    return bs_launch_kernel<&k_bs<k.D, k.DV, k.LPC, k.VPL, k.CPL, k.UCN, k.BIG, k.PK, k.WPE, false, 1024, Q8, true, EW>>(
+    return bs_launch_kernel<&k_bs<k.D, k.DV, k.LPC, k.VPL, k.CPL, k.UCN, k.BIG, k.PK, k.WPE, false, 1024, Q8, true, EW, false, L8>>(
         a, npacks, nw, lds, s);
 }
 // instance I's launch: an ES instance has the early-stop builds alone (with a plane buffer for the
 // stop-iteration words, the EW build: DESIGN 3.9); the others never see the early-stop arguments
 // The instances with the int8-LLR builds (L8): every one a plan takes by default for a decode
-// without early stop; the A/B-only entries (2, 6) and the early-stop ones have none.
+// without early stop; the A/B-only entries (2, 6) have none.  The early-stop entries (7, 8) have the
+// int8 builds of their ES and EW kernels instead (launch_bs_any; ldpc_bs.hip, bs_l8_ok).
 constexpr bool bs_l8_inst(int i) { return i == 0 || i == 1 || i == 3 || i == 4 || i == 5 || i == kBsInstUcn1; }
 // the channel a launch decodes: float LLRs, the in-prologue generator (Q8 builds) or int8 LLRs (L8)
 enum BsSrc { BS_SRC_LLR = 0, BS_SRC_GEN = 1, BS_SRC_L8 = 2 };
@@ -2088,6 +2092,13 @@ template <int I>
 int launch_bs_any(const BsLaunch& a, int npacks, int nw, size_t lds, hipStream_t s, int src, int grid, int* resident) {
     const bool q8 = src == BS_SRC_GEN;
     if (src == BS_SRC_L8) {
+        // (an early-stop instance: the int8 early-stop build, or with a plane buffer for the
+        // stop-iteration words the int8 EW build)
+        if constexpr (kBsInst[I].ES) {
+            if (a.hdx) return LDPC_ERR_UNSUPPORTED;
+            return a.hdw ? launch_bs_es_x<I, false, true, true>(a, npacks, nw, lds, s)
+                         : launch_bs_es_x<I, false, false, true>(a, npacks, nw, lds, s);
+        }
         // (resident[5 / 6]: the int8 decode and word builds; the word mode alone exports: hdx with word)
         if constexpr (bs_l8_inst(I)) {
             if (a.hdw || (a.hdx && !a.word)) return LDPC_ERR_UNSUPPORTED;

@@ -129,14 +129,15 @@ __device__ __forceinline__ void lds_dput(uint32_t addr, uint32_t x, uint32_t y) 
 // variable ORs into the pack's row in global memory: zero at the start, hd_t & nn on the few
 // iterations where codewords stop, hd_{T-1} & ~done in the last variable phase.  The ORs are
 // atomics without a return value, so no wave waits for memory inside the loop.
-// L8: the LLRs read as int8 grid values (a.llr points at bytes; as bsl's L8 build)
+// L8: the LLRs read as int8 grid values (a.llr points at bytes; as bsl's L8 build);
+// with ES / EW the int8 builds of the early-stop kernels
 template <int D, int DVH, int DVL, int LPC, int VPL, int CPL, int WPE, bool XP, int LB, bool MIX, bool B1, bool Q8,
           bool ES = false, bool EW = false, bool L8 = false>
 __global__ void __launch_bounds__(LB) __attribute__((amdgpu_waves_per_eu(WPE)))
 k_bsc(std::conditional_t<ES, std::conditional_t<EW, BscArgsEw, BscArgsEs>, std::conditional_t<XP, BscArgsXp, BscArgs>> a) {
     static_assert(!ES || (B1 && !XP), "early stop: the beta = 1 build, no export");
     static_assert(!EW || ES, "the stop-iteration word: early-stop builds");
-    static_assert(!L8 || (!Q8 && !ES), "int8 LLRs: the decode and export builds");
+    static_assert(!L8 || !Q8, "int8 LLRs: the decode, export and early-stop builds");
     constexpr int SB = (DVH * QMAX + QMAX <= 127) ? 8 : 9;
     constexpr int EPL = (D + LPC - 1) / LPC;
     constexpr int VNW = DVH + 1;
@@ -249,8 +250,9 @@ k_bsc(std::conditional_t<ES, std::conditional_t<EW, BscArgsEw, BscArgsEs>, std::
                 if (a.n_iter) a.n_iter[b0 + tid] = 0;
             }
         }
-        if constexpr (L8) {
+        if constexpr (L8 && !ES) {
             // int8 LLRs: an invalid byte has no float decode to fall back to; marked the same way
+            // (the early-stop int8 builds: by the block above, once)
             if (tid < nvalid && a.flags) a.flags[b0 + tid] = 0x80;
         }
         if (tid == 0) a.bad[blockIdx.x] = 1u;
@@ -1080,9 +1082,19 @@ static int bsc_launch(const BscLaunch& a, int nblocks, int nw, size_t lds, hipSt
     const bool b1 = bsc_b1_on() && a.beta_id && a.bcols == 1;
     const bool q8 = src == BS_SRC_GEN;
     if (src == BS_SRC_L8) {
+        // int8 LLRs, early stop: the int8 builds of the early-stop kernels below (ES, and EW with a
+        // plane buffer for the stop-iteration words), on the same terms
+        if (es) {
+            if constexpr (bsc_es_inst(I)) {
+                if (a.hdx || !a.beta_id || a.bcols != 1) return LDPC_ERR_UNSUPPORTED;
+                return a.hdw ? bsc_launch1<I, false, true, false, true, true, true>(a, nblocks, nw, lds, s)
+                             : bsc_launch1<I, false, true, false, true, false, true>(a, nblocks, nw, lds, s);
+            }
+            return LDPC_ERR_UNSUPPORTED;
+        }
         // int8 LLRs: the decode and the word build (hdx with word) of the instances a plan takes
         if constexpr (bsc_l8_inst(I)) {
-            if (es || a.hdw || (a.hdx && !a.word)) return LDPC_ERR_UNSUPPORTED;
+            if (a.hdw || (a.hdx && !a.word)) return LDPC_ERR_UNSUPPORTED;
             if (a.hdx) return b1 ? bsc_launch1<I, true, true, false, false, false, true>(a, nblocks, nw, lds, s)
                                  : bsc_launch1<I, true, false, false, false, false, true>(a, nblocks, nw, lds, s);
             return b1 ? bsc_launch1<I, false, true, false, false, false, true>(a, nblocks, nw, lds, s)
@@ -1205,7 +1217,8 @@ bool bsc_q8_ok(const DevGraph& g, const BsReq& r, bool has_short) {
 
 bool bsc_l8_ok(const DevGraph& g, const BsReq& r, bool has_short) {
     const BscPlan p = bsc_plan(g, r);
-    return p.ok && !r.es && bsc_l8_inst(p.inst) && (!has_short || p.cu > 0.f);
+    // (an early-stop plan is on an instance with early-stop builds, each with its int8 build)
+    return p.ok && (r.es ? bsc_es_inst(p.inst) : bsc_l8_inst(p.inst)) && (!has_short || p.cu > 0.f);
 }
 
 const char* bsc_kernel_name(const DevGraph& g, const BsReq& r) {

@@ -880,8 +880,10 @@ int ldpc_decode_word(ldpc_ctx* c, const float* llr_dev, int64_t B, const ldpc_de
 // ---- int8 quantized LLRs: the counters-only decode and the word mode on the
 // bit-sliced kernels' L8 builds, no v5 fixup (an invalid pack is marked by the kernel) -----------
 // the request when the L8 builds decode it (has_short: the input may hold the +-clip markers)
-static int q8_request(const ldpc_ctx* c, int64_t B, const ldpc_decode_params* p, bool has_short, BsReq* r) {
-    const int rq = bs_request(c, B, p, false, r);
+// (es: the early-stop request, served by the int8 builds of the early-stop kernels)
+static int q8_request(const ldpc_ctx* c, int64_t B, const ldpc_decode_params* p, bool has_short, BsReq* r,
+                      bool es = false) {
+    const int rq = bs_request(c, B, p, es, r);
     if (rq != LDPC_OK) return rq;
     return bs_l8_ok(c->g->dev, *r, has_short) ? LDPC_OK : LDPC_ERR_UNSUPPORTED;
 }
@@ -895,11 +897,11 @@ int ldpc_q8_supported(const ldpc_ctx* c, const ldpc_decode_params* p, int32_t ha
 }
 
 static int decode_q8_impl(ldpc_ctx* c, const int8_t* q8_dev, int64_t B, const ldpc_decode_params* p, const BsOuts& o,
-                          uint32_t* iter_wrong, void* stream) {
+                          uint32_t* iter_wrong, void* stream, bool es = false) {
     BsReq r{};
     // (markers in the input are invalid bytes where the plan has no shortened-bit path: the kernel
     // marks their packs, so the request itself is served either way)
-    const int rq = q8_request(c, B, p, false, &r);
+    const int rq = q8_request(c, B, p, false, &r, es);
     if (rq != LDPC_OK) return rq;
     r.l8 = q8_dev;
     ldpc_graph* g = c->g;
@@ -912,9 +914,12 @@ static int decode_q8_impl(ldpc_ctx* c, const int8_t* q8_dev, int64_t B, const ld
     BsOut bo{};
     bo.counters = o.counters;
     bo.flags = o.frame_flags;
-    const int st = fused_decode_bs(g->dev, b, c->fused, nullptr, r, c->B_max, c->ntiles_max, bo, o.rows, o.word_flags, s);
+    bo.n_iter = o.n_iter;
+    bo.iter_hist = o.iter_hist;
+    const int st = fused_decode_bs(g->dev, b, c->fused, nullptr, r, c->B_max, c->ntiles_max, bo, o.rows, o.word_flags, s,
+                                   o.ev);
     if (st != LDPC_OK) return st;
-    set_last_kernel(c, bs_kernel_name(g->dev, r), o.rows ? ",word" : nullptr, false);
+    set_last_kernel(c, bs_kernel_name(g->dev, r), o.ev ? ",events" : o.rows ? ",word" : nullptr, false);
     std::strncat(c->last_kernel, "+q8", sizeof(c->last_kernel) - std::strlen(c->last_kernel) - 1);
     return hipGetLastError() == hipSuccess ? LDPC_OK : LDPC_ERR_HIP;
 }
@@ -972,6 +977,38 @@ int ldpc_decode_awgn_events(ldpc_ctx* c, int64_t B, const ldpc_decode_params* p,
     if (!o->early_stop) return LDPC_ERR_UNSUPPORTED;       // (the in-prologue channel has no full-T word build)
     const EventSink ev = event_sink(o, ch->offset, p);
     return decode_awgn_es_impl(c, B, p, ch, bs_outs(o, &ev), stream);
+}
+
+// ---- int8 LLRs in the early-stop, stop-iteration-word and events modes: the float
+// entry points' outputs, decoded by the int8 builds of the early-stop kernels (events without early
+// stop: by the int8 word build and events_out) -------------------------------------------------
+int ldpc_q8_es_supported(const ldpc_ctx* c, const ldpc_decode_params* p, int32_t has_short) {
+    if (!c || !p) return LDPC_ERR_ARG;
+    BsReq r{};
+    const int st = q8_request(c, 1, p, has_short != 0, &r, true);
+    return st == LDPC_OK ? 1 : st == LDPC_ERR_UNSUPPORTED ? 0 : st;
+}
+
+int ldpc_decode_q8_es(ldpc_ctx* c, const int8_t* q8_dev, int64_t B, const ldpc_decode_params* p,
+                      const ldpc_es_outputs* o, void* stream) {
+    if (!q8_dev || !o || o->size != (int32_t)sizeof(ldpc_es_outputs)) return LDPC_ERR_ARG;
+    if (!c || !p) return LDPC_ERR_ARG;
+    return decode_q8_impl(c, q8_dev, B, p, bs_outs(o), nullptr, stream, true);
+}
+
+int ldpc_decode_q8_es_word(ldpc_ctx* c, const int8_t* q8_dev, int64_t B, const ldpc_decode_params* p,
+                           const ldpc_es_word_outputs* o, void* stream) {
+    if (!q8_dev || !o || o->size != (int32_t)sizeof(ldpc_es_word_outputs) || !o->hard_stop) return LDPC_ERR_ARG;
+    if (!c || !p) return LDPC_ERR_ARG;
+    return decode_q8_impl(c, q8_dev, B, p, bs_outs(o), nullptr, stream, true);
+}
+
+int ldpc_decode_q8_events(ldpc_ctx* c, const int8_t* q8_dev, int64_t B, const ldpc_decode_params* p,
+                          const ldpc_event_outputs* o, void* stream) {
+    if (!q8_dev || !event_outputs_ok(o)) return LDPC_ERR_ARG;
+    if (!c || !p) return LDPC_ERR_ARG;
+    const EventSink ev = event_sink(o, o->frame_base, p);
+    return decode_q8_impl(c, q8_dev, B, p, bs_outs(o, &ev), nullptr, stream, o->early_stop != 0);
 }
 
 // (include/ldpc_nms_debug.h) events_out on the caller's planes

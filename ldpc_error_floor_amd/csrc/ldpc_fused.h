@@ -125,7 +125,8 @@ struct BsOut {
 bool bs_supported(const DevGraph& g, const BsReq& r);
 bool bs_q8_ok(const DevGraph& g, const BsReq& r, bool has_short);
 // l8_ok: the int8-LLR builds (BsReq::l8) serve the request: its plan's instance has
-// them and, with has_short (the +-clip markers in the input), decodes shortened bits
+// them and, with has_short (the +-clip markers in the input), decodes shortened bits; for an
+// early-stop request, its early-stop plan's instance
 bool bs_l8_ok(const DevGraph& g, const BsReq& r, bool has_short);
 bool bsc_l8_ok(const DevGraph& g, const BsReq& r, bool has_short);
 const char* bs_kernel_name(const DevGraph& g, const BsReq& r);

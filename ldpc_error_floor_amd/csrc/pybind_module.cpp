@@ -475,6 +475,79 @@ PYBIND11_MODULE(_ldpc_nms, m) {
         },
         py::arg("ctx"), py::arg("T"), py::arg("decoding_type"), py::arg("q_bit"),
         py::arg("target_bits"), py::arg("kernel"), py::arg("clip_llr") = 20.0f, py::arg("early_stop") = false);
+    // int8 LLRs in the early-stop, stop-iteration-word and events modes (ldpc_decode_q8_es /
+    // ldpc_decode_q8_es_word / ldpc_decode_q8_events / ldpc_q8_es_supported): the
+    // arguments of decode_es / decode_es_word / decode_events, with the int8 rows for the LLRs
+    m.def(
+        "decode_q8_es",
+        [](Ctx& c, uintptr_t q8, int64_t B, int T, int decoding_type, int q_bit, int target_bits,
+           float clip, int kernel, uintptr_t counters, uintptr_t flags, uintptr_t n_iter,
+           uintptr_t iter_hist, uintptr_t stream) {
+            ldpc_decode_params p = make_params(T, decoding_type, q_bit, target_bits, clip, kernel);
+            ldpc_es_outputs o = make_es_outputs(counters, flags, n_iter, iter_hist);
+            int st;
+            {
+                py::gil_scoped_release nogil;
+                st = ldpc_decode_q8_es(c.h, reinterpret_cast<const int8_t*>(q8), B, &p, &o,
+                                       reinterpret_cast<void*>(stream));
+            }
+            check(st, "ldpc_decode_q8_es");
+        },
+        py::arg("ctx"), py::arg("q8"), py::arg("B"), py::arg("T"), py::arg("decoding_type"),
+        py::arg("q_bit"), py::arg("target_bits"), py::arg("clip"), py::arg("kernel"),
+        py::arg("counters") = 0, py::arg("flags") = 0, py::arg("n_iter") = 0, py::arg("iter_hist") = 0,
+        py::arg("stream") = 0);
+    m.def(
+        "decode_q8_es_word",
+        [](Ctx& c, uintptr_t q8, int64_t B, int T, int decoding_type, int q_bit, int target_bits,
+           float clip, int kernel, uintptr_t hard_stop, uintptr_t word_flags, uintptr_t counters,
+           uintptr_t flags, uintptr_t n_iter, uintptr_t iter_hist, uintptr_t stream) {
+            ldpc_decode_params p = make_params(T, decoding_type, q_bit, target_bits, clip, kernel);
+            ldpc_es_word_outputs o = make_es_word_outputs(hard_stop, word_flags, counters, flags, n_iter, iter_hist);
+            int st;
+            {
+                py::gil_scoped_release nogil;
+                st = ldpc_decode_q8_es_word(c.h, reinterpret_cast<const int8_t*>(q8), B, &p, &o,
+                                            reinterpret_cast<void*>(stream));
+            }
+            check(st, "ldpc_decode_q8_es_word");
+        },
+        py::arg("ctx"), py::arg("q8"), py::arg("B"), py::arg("T"), py::arg("decoding_type"),
+        py::arg("q_bit"), py::arg("target_bits"), py::arg("clip"), py::arg("kernel"),
+        py::arg("hard_stop"), py::arg("word_flags") = 0, py::arg("counters") = 0, py::arg("flags") = 0,
+        py::arg("n_iter") = 0, py::arg("iter_hist") = 0, py::arg("stream") = 0);
+    m.def(
+        "decode_q8_events",
+        [](Ctx& c, uintptr_t q8, int64_t B, int T, int decoding_type, int q_bit, int target_bits,
+           float clip, int kernel, bool early_stop, int64_t frame_base, int64_t cap, uintptr_t ev_count,
+           uintptr_t ev_frame, uintptr_t ev_info, uintptr_t ev_word, uintptr_t counters, uintptr_t flags,
+           uintptr_t n_iter, uintptr_t iter_hist, uintptr_t stream) {
+            ldpc_decode_params p = make_params(T, decoding_type, q_bit, target_bits, clip, kernel);
+            ldpc_event_outputs o = make_event_outputs(early_stop, frame_base, cap, ev_count, ev_frame, ev_info,
+                                                      ev_word, counters, flags, n_iter, iter_hist);
+            int st;
+            {
+                py::gil_scoped_release nogil;
+                st = ldpc_decode_q8_events(c.h, reinterpret_cast<const int8_t*>(q8), B, &p, &o,
+                                           reinterpret_cast<void*>(stream));
+            }
+            check(st, "ldpc_decode_q8_events");
+        },
+        py::arg("ctx"), py::arg("q8"), py::arg("B"), py::arg("T"), py::arg("decoding_type"),
+        py::arg("q_bit"), py::arg("target_bits"), py::arg("clip"), py::arg("kernel"),
+        py::arg("early_stop"), py::arg("frame_base"), py::arg("cap"), py::arg("ev_count"),
+        py::arg("ev_frame"), py::arg("ev_info"), py::arg("ev_word") = 0, py::arg("counters") = 0,
+        py::arg("flags") = 0, py::arg("n_iter") = 0, py::arg("iter_hist") = 0, py::arg("stream") = 0);
+    m.def(
+        "q8_es_supported",
+        [](Ctx& c, int T, int decoding_type, int q_bit, int target_bits, int kernel, float clip, bool has_short) {
+            ldpc_decode_params p = make_params(T, decoding_type, q_bit, target_bits, clip, kernel);
+            const int st = ldpc_q8_es_supported(c.h, &p, has_short ? 1 : 0);
+            check(st, "ldpc_q8_es_supported");
+            return st == 1;
+        },
+        py::arg("ctx"), py::arg("T"), py::arg("decoding_type"), py::arg("q_bit"),
+        py::arg("target_bits"), py::arg("kernel"), py::arg("clip_llr") = 20.0f, py::arg("has_short") = false);
     // test hook (ldpc_nms_debug.h): the event collector on caller-supplied planes
     m.def(
         "debug_events_out",

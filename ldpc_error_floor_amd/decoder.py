@@ -508,17 +508,24 @@ class NMSDecoder:
             return Q8_GRIDS[self.q_bit]
         return (1.0, 126)
 
-    def supports_q8(self, has_short: bool = False, word: bool = False, T=None, kernel=None) -> bool:
+    def supports_q8(self, has_short: bool = False, word: bool = False, T=None, kernel=None,
+                    early_stop: bool = False) -> bool:
         """Whether ``decode_q8`` runs the bit-sliced kernels' int8 builds for this decoder
         (``ldpc_q8_supported``) -- exactly where they serve the float decode of the same kind
         (counters / flags / iter_wrong, or with ``word`` the ``hard_last`` mode) -- and, with
         ``has_short``, decodes the +-clip markers of shortened bits.  Where it is false (q = 6, the
         float modes, flood, per-edge weights, other graphs) ``decode_q8`` dequantizes and calls
-        ``decode``."""
+        ``decode``.  ``early_stop=True``: whether ``decode_q8(early_stop=True)``, with or without
+        ``hard_last`` or ``events``, runs the int8 builds of the early-stop kernels
+        (``ldpc_q8_es_supported``); ``events`` without ``early_stop`` is the
+        ``word`` case."""
         T = self.T if T is None else int(T)
         if T > self.T or self.decoding_type != DECODING_QMS or self.q_bit not in Q8_GRIDS:
             return False
         ctx = self._ensure_ctx(1, T)
+        if early_stop:
+            return bool(self._ext.q8_es_supported(ctx, T, self.decoding_type, self.q_bit, self.target_bits,
+                                                  KERNELS[kernel or self.kernel], self.clip, bool(has_short)))
         return bool(self._ext.q8_supported(ctx, T, self.decoding_type, self.q_bit, self.target_bits,
                                            KERNELS[kernel or self.kernel], self.clip, bool(has_short), bool(word)))
 
@@ -593,7 +600,8 @@ class NMSDecoder:
     def decode_q8(self, q8, T: Optional[int] = None, counters=None, flags=False, iter_wrong: bool = False,
                   hard_last=False, word_flags: bool = False, kernel: Optional[str] = None, stream=None,
                   on_invalid: str = "raise", app: bool = False, hard: bool = False, synd: bool = False,
-                  target_bits: Optional[int] = None) -> DecodeResult:
+                  target_bits: Optional[int] = None, early_stop: bool = False, n_iter: bool = False,
+                  iter_hist=None, events=None, frame_base: int = 0) -> DecodeResult:
         """Decode int8 quantized LLRs: ``q8`` is int8 ``[B, N*z]``, the LLR in grid
         units ``g = LLR / step`` with ``-qmax <= g <= qmax``, -128 / +127 for a shortened bit's
         -clip / +clip (``quantize_q8`` makes it, ``awgn_q8`` generates it).  Every output equals,
@@ -608,10 +616,19 @@ class NMSDecoder:
         and raises ``ValueError`` naming the first such frame; ``"mark"`` returns the result as it
         is.
 
+        ``early_stop`` / ``n_iter`` / ``iter_hist`` / ``events`` / ``frame_base``
+        mean what they mean in ``decode``, with ``hard_last`` the stop-iteration words, and are
+        refused as there: ``iter_wrong`` (and ``app`` / ``hard`` / ``synd``) not with
+        ``early_stop``, ``n_iter`` / ``iter_hist`` only with it, ``events`` without ``hard_last`` /
+        ``word_flags``.  The int8 builds of the early-stop kernels decode them (``events`` without
+        ``early_stop``: the int8 word build), each output bit for bit ``decode``'s of
+        ``dequantize_q8(q8)`` in the same mode.  A marked pack has ``n_iter`` 0 and no event, and
+        enters neither the counters nor ``iter_hist``.
+
         Where ``supports_q8`` is false, or ``app`` / ``hard`` / ``synd`` is asked for, the bytes are
-        dequantized and ``decode`` runs (``last_kernel()`` tells); invalid bytes are then checked
-        on the device for ``"raise"`` and decoded as ``decode`` decodes off-grid LLRs for
-        ``"mark"``."""
+        dequantized and ``decode`` runs with the same mode arguments (``last_kernel()`` tells);
+        invalid bytes are then checked on the device for ``"raise"`` and decoded as ``decode``
+        decodes off-grid LLRs for ``"mark"``."""
         torch = self._torch
         if on_invalid not in ("raise", "mark"):
             raise ValueError("on_invalid must be 'raise' or 'mark'")
@@ -624,9 +641,30 @@ class NMSDecoder:
             raise ValueError("word_flags is an output of hard_last=True")
         if word and iter_wrong:
             raise ValueError("hard_last serves word_flags, counters and flags only, not iter_wrong")
+        want_hist = iter_hist is not None and iter_hist is not False
+        if events is not None:
+            bad = [k for k, v in dict(hard_last=word, app=app, hard=hard, synd=synd, iter_wrong=iter_wrong,
+                                      word_flags=word_flags).items() if v]
+            if not early_stop:
+                bad += [k for k, v in dict(n_iter=n_iter, iter_hist=want_hist).items() if v]
+            if bad:
+                raise ValueError("events serves counters and flags (with early_stop: n_iter and iter_hist) only, "
+                                 "not " + ", ".join(bad))
+        elif early_stop:
+            self._es_check_exports(app=app, hard=hard, synd=synd, iter_wrong=iter_wrong)
+        elif n_iter or want_hist:
+            raise ValueError("n_iter and iter_hist are outputs of early_stop=True")
         q8 = self._as_q8(q8)
         B = int(q8.shape[0])
-        if app or hard or synd or not self.supports_q8(word=word, T=T, kernel=kernel):
+        mode = early_stop or events is not None
+        # (the mode arguments reach decode only where one is asked for: the plain call is unchanged)
+        mode_kw = dict(early_stop=early_stop, n_iter=n_iter, iter_hist=iter_hist, events=events,
+                       frame_base=frame_base) if mode else {}
+        if early_stop:
+            served = self.supports_q8(T=T, kernel=kernel, early_stop=True)
+        else:
+            served = self.supports_q8(word=word or events is not None, T=T, kernel=kernel)
+        if app or hard or synd or not served:
             if on_invalid == "raise" and B:
                 badrows = self._q8_invalid_rows(q8)
                 if bool(badrows.any().item()):
@@ -636,7 +674,11 @@ class NMSDecoder:
             return self.decode(self.dequantize_q8(q8), T=T, app=bool(app), hard=hard, synd=synd, counters=counters,
                                flags=flags, kernel=kernel, stream=stream, target_bits=target_bits,
                                iter_wrong=iter_wrong, hard_last=hard_last, word_flags=word_flags,
-                               on_off_grid="mark")
+                               on_off_grid="mark", **mode_kw)
+        if mode:
+            return self._decode_q8_mode(q8, B, T, nt, early_stop, hard_last if word else None, word_flags, events,
+                                        frame_base, counters, flags, n_iter, iter_hist, kernel, stream,
+                                        on_invalid == "raise")
         dev = self.device
         res = self._word_result(B, hard_last) if word else DecodeResult()
         asked = flags is not None and flags is not False
@@ -660,6 +702,48 @@ class NMSDecoder:
             self._ext.decode_q8(ctx, q8.data_ptr(), B, T, self.decoding_type, self.q_bit, nt, self.clip,
                                 KERNELS[kernel or self.kernel], ptr(res.counters), ptr(res.flags),
                                 ptr(res.iter_wrong), stream.cuda_stream)
+        if check:
+            stream.synchronize()
+            marked = (res.flags[:B] == 0x80).nonzero()
+            if marked.numel():
+                raise ValueError(f"decode_q8: frame {int(marked[0].item())} is the first of {int(marked.numel())} "
+                                 "frames in packs holding a byte that is no q8 value; they were not decoded "
+                                 "(on_invalid='mark' returns them marked)")
+            if not asked:
+                res.flags = None
+        return res
+
+    def _decode_q8_mode(self, q8, B, T, nt, early_stop, hard_last, word_flags, events, frame_base, counters,
+                        flags, n_iter, iter_hist, kernel, stream, check):
+        """``decode_q8``'s early-stop, stop-iteration-word and events decodes on the int8 builds
+        (DESIGN.md 3.12): the outputs of ``decode`` in the same mode; ``check``: wait and raise on a
+        marked pack (``frame_flags`` 0x80)."""
+        torch = self._torch
+        dev = self.device
+        if events is not None and (events.device != dev or events.n_vars != self.n_vars):
+            raise ValueError("events must be an EventBuffer of this decoder")
+        res = self._word_result(B, hard_last) if hard_last is not None else DecodeResult()
+        asked = flags is not None and flags is not False
+        self._es_outputs(res, B, T, counters, flags if asked else check, n_iter if early_stop else False,
+                         iter_hist if early_stop else None)
+        if hard_last is not None and word_flags:
+            res.word_flags = torch.empty(B, dtype=torch.uint8, device=dev)
+        if B == 0:
+            return res
+        ctx = self._ensure_ctx(B, T)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        ptr = lambda t: 0 if t is None else t.data_ptr()   # noqa: E731
+        head = (ctx, q8.data_ptr(), B, T, self.decoding_type, self.q_bit, nt, self.clip, KERNELS[kernel or self.kernel])
+        tail = (ptr(res.counters), ptr(res.flags), ptr(res.n_iter), ptr(res.iter_hist), stream.cuda_stream)
+        if events is not None:
+            self._ext.decode_q8_events(*head, bool(early_stop), int(frame_base), events.cap, events.ev_count.data_ptr(),
+                                       events.ev_frame.data_ptr(), events.ev_info.data_ptr(), ptr(events.ev_word),
+                                       *tail)
+        elif hard_last is not None:
+            self._ext.decode_q8_es_word(*head, res.hard_last.data_ptr(), ptr(res.word_flags), *tail)
+        else:
+            self._ext.decode_q8_es(*head, *tail)
         if check:
             stream.synchronize()
             marked = (res.flags[:B] == 0x80).nonzero()
